@@ -18,9 +18,17 @@ ranks' objectives sum to the single-process ELBO of the global minibatch and the
 with one RCCL all-reduce.
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field definitions).  `dtype` "f32" names the arithmetic of the
-dominant kernels and of every stored tensor of the layers; `roofline` prices the float32 GEMM family against the data-sheet
-157.3 TFLOP/s and also reports what a register-only MFMA loop sustains on the box at hand (`sustained_mfma_measured`);
-`f64acc_projection` / `i8_projection` are the same objects for the float64-accumulating and the int8 products of the step.
+dominant kernels and of every stored tensor of the layers.  A plain run sets up, warms up, times the steps and prints the line
+(`value`, `ms_per_step`, `final_loss`, ...).  `--full` adds what takes runs of its own: `roofline` prices the float32 GEMM
+family (an instrumented eager re-run of the steps) against the data-sheet 157.3 TFLOP/s and also reports what a register-only
+MFMA loop sustains on the box at hand (`sustained_mfma_measured`); `f64acc_projection` / `i8_projection` are the same objects
+for the float64-accumulating and the int8 products of the step; on one GPU also the Gibbs build + Cholesky table, the two
+secondary training steps and the CPU baseline (unless --no-build-chol / --no-cpu-baseline).
+
+`--dump-outputs DIR` writes what the last timed step computed, before anything else runs: `loss.npy` (float64, the
+global objective), `param.<name>.npy` (the parameters after its Adam update) and `grad.<name>.npy` (the gradient that update
+consumed), float32, about 25 MB in all.  Inputs, initial parameters and noise are seeded, so two builds can be compared
+array for array.
 """
 import argparse
 import json
@@ -136,6 +144,26 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return max(1, n)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, opt, loss_total):
+    """What the last timed step handed back: the objective, the updated parameters and the gradient Adam consumed."""
+    import numpy as np
+    arrays = {'loss': loss_total.detach().double().cpu().numpy()}
+    grad_of = {id(p): g for p, g in zip(opt.bucket.params, opt.bucket.grad_views)}
+    for name, p in model.named_parameters():
+        arrays[f'param.{name}'] = p.detach().float().cpu().numpy()
+        if id(p) in grad_of:
+            arrays[f'grad.{name}'] = grad_of[id(p)].detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f'{name}.npy'), a)
 
 
 def cpu_baseline(x, y, idx, seconds_budget=14.0, mirror=True):
@@ -521,7 +549,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: roofline / per-family GEMM figures (instrumented re-run, '
+                         'MFMA rate probe) and, on one GPU, the Gibbs build + Cholesky table, the secondary steps and the '
+                         'CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss, parameters and gradients of the last timed step to DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full (or --config cfg5): skip the CPU baseline')
     ap.add_argument('--config', choices=('cfg4', 'cfg5'), default='cfg4',
                     help='cfg4 (default): BASELINE configs[3], the headline 2-layer M=1024 workload; cfg5: configs[4], the 3-layer '
                          'M=2048 N=1e6 shape on ONE GPU (tools/dsvi_cfg5_probe.py), see --forward')
@@ -529,7 +563,7 @@ def main():
                     help="cfg5 only: settings.forward_precision -- configs[4]'s bf16 forward")
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly (no hipGraph replay)')
     ap.add_argument('--no-build-chol', action='store_true',
-                    help='skip the Gibbs-build + Cholesky fields (PMC passes of the DSVI step only)')
+                    help='--full: skip the Gibbs-build + Cholesky fields (PMC passes of the DSVI step only)')
     ap.add_argument('--scaling', choices=('weak', 'strong'), default='strong',
                     help='strong (default, SURVEY 8e): ONE 4096-row minibatch is split over the N GPUs (4096/N rows each), '
                          'value = iterations/s; weak: every GPU takes its own 4096-row minibatch per iteration (global batch '
@@ -558,8 +592,12 @@ def main():
                          'minibatch, the objective scaled as on rank 0 of G; no collective).  The JSON line is marked '
                          '"analysis" and is not a result for --gpus G.')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
 
     if args.config == 'cfg5':
+        if args.dump_outputs:
+            raise SystemExit('--dump-outputs is for the headline workload (cfg4)')
         return main_cfg5(args)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -780,28 +818,29 @@ def main():
         if world > 1:                                   # the ranks' objectives SUM to the single-GPU loss (nsgp/dist.py)
             dist.all_reduce(loss_total, op=dist.ReduceOp.SUM)
         final_loss = float(loss_total.item())
+        if args.dump_outputs and rank == 0:                 # before the instrumented re-run below moves the parameters
+            dump_outputs(args.dump_outputs, model, opt, loss_total)
 
-        # roofline of the dominant kernel family: re-run the same steps EAGERLY with HIP events around
-        # every GEMM launch (kept out of the timed region above)
-        timer = GemmTimer()
-        ops.set_gemm_timer(timer)
-        nprof = min(args.steps, 5)
-        for k in range(nprof):
-            x_in.copy_(xs[k % n_batches]); y_in.copy_(ys[k % n_batches])
-            fwd_bwd()
-            dp.allreduce_grads(gather=False)
-            adam_step()
-        gemm_ms, gemm_flops, gemm_launches = timer.summary(torch.float32)
-        g64_ms, g64_flops, g64_launches = timer.summary(torch.float64)
-        acc_ms, acc_flops, acc_launches = timer.summary('f64acc')
-        i8_ms, i8_flops, i8_launches = timer.summary('i8')
-        ops.set_gemm_timer(None)
+        if args.full:
+            # roofline of the dominant kernel family: re-run the same steps EAGERLY with HIP events around
+            # every GEMM launch (kept out of the timed region above)
+            timer = GemmTimer()
+            ops.set_gemm_timer(timer)
+            nprof = min(args.steps, 5)
+            for k in range(nprof):
+                x_in.copy_(xs[k % n_batches]); y_in.copy_(ys[k % n_batches])
+                fwd_bwd()
+                dp.allreduce_grads(gather=False)
+                adam_step()
+            gemm_ms, gemm_flops, gemm_launches = timer.summary(torch.float32)
+            g64_ms, g64_flops, g64_launches = timer.summary(torch.float64)
+            acc_ms, acc_flops, acc_launches = timer.summary('f64acc')
+            i8_ms, i8_flops, i8_launches = timer.summary('i8')
+            ops.set_gemm_timer(None)
 
     result = None
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12
-        sus = mfma_sustained(device)
         result = {
             # a "step" is one fwd+ELBO+bwd+Adam pass over a 4096-row minibatch.  Weak scaling: an N-GPU iteration is N
             # such passes (one per rank, global batch 4096 N) joined by one RCCL all-reduce, so value = N x iterations/s;
@@ -836,56 +875,61 @@ def main():
             **({'analysis': f'one rank\'s share of a {share}-rank job (rows [0, {hi - lo}) of each minibatch), '
                             'no collective; NOT a --gpus result'} if share > 1 else {}),
             'final_loss': round(final_loss, 5),
-            'roofline': {'bound': 'mfma', 'kernel': 'gemm_kernel<float,128,128,*,*> (all f32 GEMM launches of a step)',
-                         'achieved': round(achieved, 2), 'peak': MFMA_F32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                         'frac': round(achieved / MFMA_F32_PEAK_TFLOPS, 4), **gemm_traffic(world, share),
-                         # context, not the contract's `peak`: the rate a register-only MFMA loop sustains on this chip, and
-                         # the clock it holds meanwhile (the 157.3 above assumes 2.4 GHz)
-                         'sustained_mfma_measured': sus['f32']['rate'], 'clock_GHz_under_mfma_load': sus['f32']['clock_GHz'],
-                         'frac_of_sustained': round(achieved / sus['f32']['rate'], 4),
-                         'gemm_ms_per_step': round(gemm_ms / nprof, 3),
-                         'gemm_launches_per_step': gemm_launches // nprof,
-                         'algorithmic_gflop_per_step': round(gemm_flops / nprof / 1e9, 2),
-                         'f64_gemm_ms_per_step': round(g64_ms / nprof, 3),
-                         'f64_gemm_launches_per_step': g64_launches // nprof},
-            # the whitened projection A = L^-1 Kzx, accumulated in float64 on the float32 Kzx (settings.whiten_matmul_f64):
-            # float64 MFMA, priced against the 78.6 TFLOP/s float64 matrix peak
-            'f64acc_projection': ({'ms_per_step': round(acc_ms / nprof, 3), 'launches_per_step': acc_launches // nprof,
-                                   'algorithmic_gflop_per_step': round(acc_flops / nprof / 1e9, 2),
-                                   'achieved': round(acc_flops / (acc_ms * 1e-3) / 1e12, 2), 'peak': MFMA_F64_PEAK_TFLOPS,
-                                   'unit': 'TFLOP/s', 'frac': round(acc_flops / (acc_ms * 1e-3) / 1e12 / MFMA_F64_PEAK_TFLOPS, 4),
-                                   'sustained_mfma_measured': sus['f64']['rate'],
-                                   'frac_of_sustained': round(acc_flops / (acc_ms * 1e-3) / 1e12 / sus['f64']['rate'], 4)}
-                                  if acc_launches else None),
-            # the same projection on the int8 matrix cores (settings.whiten_matmul_i8, default): exact digit-plane products.
-            # `achieved` counts the int8 operations actually issued (14 plane products per multiply-add of the float64
-            # product it replaces; 15 for layers with five Kzx planes are counted as 14) against the 5 POP/s dense int8 peak;
-            # `f64_equivalent_TFLOPs` is the float64 product's flops over the same time (the float64 MFMA peak is 78.6)
-            'i8_projection': ({'ms_per_step': round(i8_ms / nprof, 3), 'launches_per_step': i8_launches // nprof,
-                               'algorithmic_gflop_per_step': round(i8_flops / nprof / 1e9, 2),
-                               'achieved': round(I8_PLANE_PRODUCTS * i8_flops / (i8_ms * 1e-3) / 1e12, 1), 'peak': MFMA_I8_PEAK_TOPS,
-                               'unit': 'TOP/s (int8)', 'frac': round(I8_PLANE_PRODUCTS * i8_flops / (i8_ms * 1e-3) / 1e12 / MFMA_I8_PEAK_TOPS, 4),
-                               'f64_equivalent_TFLOPs': round(i8_flops / (i8_ms * 1e-3) / 1e12, 2),
-                               'sustained_mfma_measured': sus['i8']['rate'],
-                               'frac_of_sustained': round(I8_PLANE_PRODUCTS * i8_flops / (i8_ms * 1e-3) / 1e12 / sus['i8']['rate'], 4)}
-                              if i8_launches else None),
         }
-        if world == 1:
-            if not args.no_build_chol:
-                result.update(gibbs_chol_ms(device))
-            if not args.no_cpu_baseline:
-                torch.set_num_threads(host_cores())
-                v, nsteps = cpu_baseline(x_all, y_all, idx, mirror=True)
-                v2, nsteps2 = cpu_baseline(x_all, y_all, idx, mirror=False)
-                result['cpu_baseline'] = {'value': round(v, 4), 'unit': 'steps/s', 'cores': torch.get_num_threads(),
-                                          'kind': 'port',
-                                          'sample': f'{nsteps} full DSVI steps (first discarded) of the same '
-                                                    'M=1024/S=10/B=4096 workload, oracle in gpytorch-mirror mode',
-                                          # the same arithmetic WITHOUT the [recalled] per-sample Kzz / Cholesky recomputation
-                                          'value_no_mirror': round(v2, 4),
-                                          'sample_no_mirror': f'{nsteps2} steps, Kzz + Cholesky once per layer'}
-                result['speedup_vs_cpu'] = round(result['value'] / v, 1)
-                result['speedup_vs_cpu_no_mirror'] = round(result['value'] / v2, 1)
+        if args.full:
+            achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12
+            sus = mfma_sustained(device)
+            result.update({
+                'roofline': {'bound': 'mfma', 'kernel': 'gemm_kernel<float,128,128,*,*> (all f32 GEMM launches of a step)',
+                             'achieved': round(achieved, 2), 'peak': MFMA_F32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                             'frac': round(achieved / MFMA_F32_PEAK_TFLOPS, 4), **gemm_traffic(world, share),
+                             # context, not the contract's `peak`: the rate a register-only MFMA loop sustains on this chip, and
+                             # the clock it holds meanwhile (the 157.3 above assumes 2.4 GHz)
+                             'sustained_mfma_measured': sus['f32']['rate'], 'clock_GHz_under_mfma_load': sus['f32']['clock_GHz'],
+                             'frac_of_sustained': round(achieved / sus['f32']['rate'], 4),
+                             'gemm_ms_per_step': round(gemm_ms / nprof, 3),
+                             'gemm_launches_per_step': gemm_launches // nprof,
+                             'algorithmic_gflop_per_step': round(gemm_flops / nprof / 1e9, 2),
+                             'f64_gemm_ms_per_step': round(g64_ms / nprof, 3),
+                             'f64_gemm_launches_per_step': g64_launches // nprof},
+                # the whitened projection A = L^-1 Kzx, accumulated in float64 on the float32 Kzx (settings.whiten_matmul_f64):
+                # float64 MFMA, priced against the 78.6 TFLOP/s float64 matrix peak
+                'f64acc_projection': ({'ms_per_step': round(acc_ms / nprof, 3), 'launches_per_step': acc_launches // nprof,
+                                       'algorithmic_gflop_per_step': round(acc_flops / nprof / 1e9, 2),
+                                       'achieved': round(acc_flops / (acc_ms * 1e-3) / 1e12, 2), 'peak': MFMA_F64_PEAK_TFLOPS,
+                                       'unit': 'TFLOP/s', 'frac': round(acc_flops / (acc_ms * 1e-3) / 1e12 / MFMA_F64_PEAK_TFLOPS, 4),
+                                       'sustained_mfma_measured': sus['f64']['rate'],
+                                       'frac_of_sustained': round(acc_flops / (acc_ms * 1e-3) / 1e12 / sus['f64']['rate'], 4)}
+                                      if acc_launches else None),
+                # the same projection on the int8 matrix cores (settings.whiten_matmul_i8, default): exact digit-plane products.
+                # `achieved` counts the int8 operations actually issued (14 plane products per multiply-add of the float64
+                # product it replaces; 15 for layers with five Kzx planes are counted as 14) against the 5 POP/s dense int8 peak;
+                # `f64_equivalent_TFLOPs` is the float64 product's flops over the same time (the float64 MFMA peak is 78.6)
+                'i8_projection': ({'ms_per_step': round(i8_ms / nprof, 3), 'launches_per_step': i8_launches // nprof,
+                                   'algorithmic_gflop_per_step': round(i8_flops / nprof / 1e9, 2),
+                                   'achieved': round(I8_PLANE_PRODUCTS * i8_flops / (i8_ms * 1e-3) / 1e12, 1), 'peak': MFMA_I8_PEAK_TOPS,
+                                   'unit': 'TOP/s (int8)', 'frac': round(I8_PLANE_PRODUCTS * i8_flops / (i8_ms * 1e-3) / 1e12 / MFMA_I8_PEAK_TOPS, 4),
+                                   'f64_equivalent_TFLOPs': round(i8_flops / (i8_ms * 1e-3) / 1e12, 2),
+                                   'sustained_mfma_measured': sus['i8']['rate'],
+                                   'frac_of_sustained': round(I8_PLANE_PRODUCTS * i8_flops / (i8_ms * 1e-3) / 1e12 / sus['i8']['rate'], 4)}
+                                  if i8_launches else None)
+            })
+            if world == 1:
+                if not args.no_build_chol:
+                    result.update(gibbs_chol_ms(device))
+                if not args.no_cpu_baseline:
+                    torch.set_num_threads(host_cores())
+                    v, nsteps = cpu_baseline(x_all, y_all, idx, mirror=True)
+                    v2, nsteps2 = cpu_baseline(x_all, y_all, idx, mirror=False)
+                    result['cpu_baseline'] = {'value': round(v, 4), 'unit': 'steps/s', 'cores': torch.get_num_threads(),
+                                              'kind': 'port',
+                                              'sample': f'{nsteps} full DSVI steps (first discarded) of the same '
+                                                        'M=1024/S=10/B=4096 workload, oracle in gpytorch-mirror mode',
+                                              # the same arithmetic WITHOUT the [recalled] per-sample Kzz / Cholesky recomputation
+                                              'value_no_mirror': round(v2, 4),
+                                              'sample_no_mirror': f'{nsteps2} steps, Kzz + Cholesky once per layer'}
+                    result['speedup_vs_cpu'] = round(result['value'] / v, 1)
+                    result['speedup_vs_cpu_no_mirror'] = round(result['value'] / v2, 1)
         print(json.dumps(result), flush=True)
     if world > 1 or rehearse:
         dist.barrier()

@@ -137,14 +137,14 @@ def test_staged_backward_with_overlapped_exchange_equals_single_process(tmp_path
         assert float((a['p'] - b['p']).abs().mean()) < 2e-5
 
 
-def _bench_line(nproc, extra, port):
+def _bench_line(nproc, extra, port, full=True):
     """Run bench.py the way the driver launches it (torch.distributed.run for N > 1) and return its JSON line."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NSGP_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    common = ['--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-build-chol'] + extra
+    common = ['--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-build-chol'] + (['--full'] if full else []) + extra
     if nproc == 1:
         cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1'] + common
     else:
@@ -188,6 +188,31 @@ def test_bench_two_rank_control_flow_matches_one_rank():
     weak = _bench_line(2, ['--scaling', 'weak'], _free_port())
     assert weak['scaling'] == 'weak' and weak['config']['global_batch'] == 8192
     assert weak['value'] == pytest.approx(2 * weak['iterations_per_sec'], rel=1e-3)
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain bench.py run times the steps and prints the headline fields only (the roofline re-run is --full's);
+    --dump-outputs writes the last timed step's loss, parameters and gradients, the same in a plain and a --full run
+    (seeded inputs; the dump is taken before the --full re-run moves the parameters)."""
+    if not torch.cuda.is_available():
+        pytest.skip('no GPU')
+    import numpy as np
+    plain = _bench_line(1, ['--dump-outputs', str(tmp_path / 'plain')], 0, full=False)
+    full = _bench_line(1, ['--dump-outputs', str(tmp_path / 'full')], 0)
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in plain
+    assert plain['steps'] == 3 and plain['ms_per_step'] == pytest.approx(1e3 / plain['value'], rel=1e-2)
+    assert 'roofline' not in plain and 'roofline' in full
+    names = sorted(os.listdir(tmp_path / 'plain'))
+    assert names == sorted(os.listdir(tmp_path / 'full'))
+    assert 'loss.npy' in names and any(n.startswith('param.') for n in names) and any(n.startswith('grad.') for n in names)
+    assert sum(os.path.getsize(tmp_path / 'plain' / n) for n in names) <= 64 << 20
+    loss = np.load(tmp_path / 'plain' / 'loss.npy')
+    assert loss.dtype == np.float64 and float(loss[0]) == pytest.approx(plain['final_loss'], rel=1e-5)
+    for n in names:
+        a, b = np.load(tmp_path / 'plain' / n), np.load(tmp_path / 'full' / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+        np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-6, err_msg=n)
 
 
 def test_gradient_sinks_fill_the_bucket_without_a_copy_and_match_plain_autograd():
