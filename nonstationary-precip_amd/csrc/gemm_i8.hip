@@ -8,7 +8,7 @@
 // (v_mfma_i32_32x32x32_i8) is 64x the float64 rate per multiply-add, and integer accumulation is EXACT.  So:
 //
 //   W[m][k]  = wsc[m] * sum_{a<5}  dW_a[m][k] 128^-a    dW_a in [-64, 64]  (wsc[m] = 2^e / 64 >= max_k |W[m][k]| / 64)
-//   K[k][j]  = ksc    * sum_{b<SK} dK_b[k][j] 128^-b    dK_b in [-64, 64]  (ksc    = 2^e / 64 >= os / 64: 0 < K <= os)
+//   K[k][j]  = ksc    * sum_{b<SK} dK_b[k][j] 128^-b    dK_b in [-64, 64]  (ksc    = 2^e / 64 >= |os| / 64: |K| <= |os|)
 //   A[m][j]  = wsc[m] ksc sum_{l<LEV} 128^-l  sum_{a+b=l} sum_k dW_a[m][k] dK_b[k][j]
 //
 // in two instantiations: SK = 4 planes of Kzx, LEV = 5 levels (14 digit-plane products) for a layer whose output feeds the
@@ -58,20 +58,24 @@ __global__ __launch_bounds__(256) void i8_slice_w_kernel(const double* __restric
         return;
     }
     const double* row = W + (b * M + m) * M;
+    // NaN-propagating maximum (a plain v > mx skips NaN): a row with a NaN or an infinity -- W of a Kzz that is not positive
+    // definite -- gets the scale NaN and zero digits, so the product's epilogue (v *= wsc ksc) makes that row of A NaN
+    const auto nmax = [](double a, double c) { return (a > c || a != a) ? a : c; };
     double mx = 0.0;
-    for (int64_t k = threadIdx.x; k <= m; k += 256) { const double v = fabs(row[k]); mx = v > mx ? v : mx; }
+    for (int64_t k = threadIdx.x; k <= m; k += 256) mx = nmax(fabs(row[k]), mx);
     // block max through LDS
-    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(mx, off, 64); mx = o > mx ? o : mx; }
+    for (int off = 32; off > 0; off >>= 1) mx = nmax(__shfl_xor(mx, off, 64), mx);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mx;
     __syncthreads();
-    mx = fmax(fmax(lds[0], lds[1]), fmax(lds[2], lds[3]));
+    mx = nmax(nmax(lds[0], lds[1]), nmax(lds[2], lds[3]));
+    const bool fin = mx <= 1.7976931348623157e308;          // false for NaN and +inf
     int e = 0;
-    (void)frexp(mx, &e);                                    // mx = f 2^e, f in [0.5, 1)  ->  2^e >= mx
-    const double rs = mx > 0.0 ? ldexp(1.0, e) : 1.0;
-    if (threadIdx.x == 0) wsc[b * M + m] = rs / 64.0;
+    (void)frexp(fin ? mx : 0.0, &e);                        // mx = f 2^e, f in [0.5, 1)  ->  2^e >= mx
+    const double rs = (fin && mx > 0.0) ? ldexp(1.0, e) : 1.0;
+    if (threadIdx.x == 0) wsc[b * M + m] = fin ? rs / 64.0 : __builtin_nan("");
     const double inv = 64.0 / rs;
     for (int64_t k = threadIdx.x; k < KB * 32; k += 256) {
-        double t = (k <= m && k < M) ? row[k] * inv : 0.0;
+        double t = (fin && k <= m && k < M) ? row[k] * inv : 0.0;
         const int64_t o = ((k >> 5) * 2 + ((k >> 4) & 1)) * Mp * 16 + m * 16 + (k & 15);
 #pragma unroll
         for (int a = 0; a < I8_SW; ++a) {
@@ -84,6 +88,9 @@ __global__ __launch_bounds__(256) void i8_slice_w_kernel(const double* __restric
 
 // ---- digit planes of Kzx, evaluated in float64 from the float32 kernel inputs ------------------------------------
 // One thread = one column j and one k-block of 32: K[k][j] = os exp(-1/2 sum_d ((z[k][d] - x[j][d]) / ls[d])^2).
+// Digit scale: every workgroup (256 columns x one k-block) writes its own slot ksc[b][kb][blockIdx.x] -- os's power of two / 64,
+// or NaN when os or an ls is not finite or one of its entries came out NaN (a NaN z or x).  One writer per slot, so a NaN
+// cannot be overwritten by another workgroup's finite value; the product folds the slots of the k-blocks a tile reads.
 template <int D, int SK>
 __global__ __launch_bounds__(256) void i8_rbf_build_kernel(const float* __restrict__ Z, const float* __restrict__ x, int64_t sx,
                                                            const float* __restrict__ ls, const float* __restrict__ os,
@@ -93,52 +100,64 @@ __global__ __launch_bounds__(256) void i8_rbf_build_kernel(const float* __restri
     const int64_t b = blockIdx.z, kb = blockIdx.y;
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     __shared__ double zs[32][D];
+    __shared__ int bad;
+    if (threadIdx.x == 0) bad = 0;
     if (threadIdx.x < 32 * D) {
         const int kk = threadIdx.x / D, d = threadIdx.x % D;
         const int64_t k = kb * 32 + kk;
         zs[kk][d] = k < M ? (double)Z[(b * M + k) * D + d] / (double)ls[b * D + d] : 0.0;
     }
     __syncthreads();
-    if (j >= np) return;
     const double osd = (double)os[b];
+    bool fin = fabs(osd) <= 1.7976931348623157e308;
+#pragma unroll
+    for (int d = 0; d < D; ++d) fin = fin && fabs((double)ls[b * D + d]) <= 1.7976931348623157e308;
     int e = 0;
-    (void)frexp(osd, &e);
-    const double cs = ldexp(1.0, e);                        // >= os
-    if (j == 0 && kb == 0) ksc[b] = cs / 64.0;
-    const double sc = osd * 64.0 / cs;
-    double xs[D];
+    (void)frexp(fin ? osd : 0.0, &e);
+    const double cs = ldexp(1.0, e);                        // >= |os|
+    const double sc = fin ? osd * 64.0 / cs : 0.0;
+    if (j < np) {
+        double xs[D];
 #pragma unroll
-    for (int d = 0; d < D; ++d) xs[d] = j < n ? (double)x[b * sx + j * D + d] / (double)ls[b * D + d] : 0.0;
-    signed char* out = Kd + b * (int64_t)SK * KB * 2 * np * 16;
-    const int64_t plane = KB * 2 * np * 16;
+        for (int d = 0; d < D; ++d) xs[d] = j < n ? (double)x[b * sx + j * D + d] / (double)ls[b * D + d] : 0.0;
+        signed char* out = Kd + b * (int64_t)SK * KB * 2 * np * 16;
+        const int64_t plane = KB * 2 * np * 16;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        int pk[SK][4] = {};
+        for (int h = 0; h < 2; ++h) {
+            int pk[SK][4] = {};
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int kk = h * 16 + q;
-            double r2 = 0.0;
+            for (int q = 0; q < 16; ++q) {
+                const int kk = h * 16 + q;
+                double r2 = 0.0;
 #pragma unroll
-            for (int d = 0; d < D; ++d) { const double df = zs[kk][d] - xs[d]; r2 = __builtin_fma(df, df, r2); }
-            const bool in = j < n && kb * 32 + kk < M;
-            const double ev = in ? t_fexp<double>(-0.5 * r2) : 0.0;
-            // the float32 Kzx the backward pass needs for Wbar = tril(Abar Kzx^T), rounded from the float64 value (the forward
-            // pass itself never reads it): saves the backward's own build launch
-            if (Kf && in) Kf[(b * M + kb * 32 + kk) * n + j] = (float)(osd * ev);
-            double t = sc * ev;
+                for (int d = 0; d < D; ++d) { const double df = zs[kk][d] - xs[d]; r2 = __builtin_fma(df, df, r2); }
+                const bool in = j < n && kb * 32 + kk < M;
+                const bool nan_e = in && r2 != r2;
+                if (nan_e) bad = 1;
+                const double ev = in ? t_fexp<double>(-0.5 * r2) : 0.0;
+                const double evd = nan_e ? 0.0 : ev;          // (no NaN into the digit cutter's float -> int conversions)
+                // the float32 Kzx the backward pass needs for Wbar = tril(Abar Kzx^T), rounded from the float64 value (the
+                // forward pass itself never reads it): saves the backward's own build launch
+                if (Kf && in) Kf[(b * M + kb * 32 + kk) * n + j] = (float)(osd * ev);
+                // (the product stays free to fuse into the first plane's t - dg, as it always has: digits bit-identical)
+                double t = sc * evd;
+#pragma unroll
+                for (int s = 0; s < SK; ++s) {
+                    const double dg = rint(t);
+                    pk[s][q >> 2] |= ((int)dg & 0xFF) << (8 * (q & 3));
+                    t = (t - dg) * 128.0;
+                }
+            }
 #pragma unroll
             for (int s = 0; s < SK; ++s) {
-                const double dg = rint(t);
-                pk[s][q >> 2] |= ((int)dg & 0xFF) << (8 * (q & 3));
-                t = (t - dg) * 128.0;
+                v4i v = {pk[s][0], pk[s][1], pk[s][2], pk[s][3]};
+                *reinterpret_cast<v4i*>(out + s * plane + (kb * 2 + h) * np * 16 + j * 16) = v;
             }
         }
-#pragma unroll
-        for (int s = 0; s < SK; ++s) {
-            v4i v = {pk[s][0], pk[s][1], pk[s][2], pk[s][3]};
-            *reinterpret_cast<v4i*>(out + s * plane + (kb * 2 + h) * np * 16 + j * 16) = v;
-        }
     }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        ksc[(b * KB + kb) * gridDim.x + blockIdx.x] = (fin && !bad) ? cs / 64.0 : __builtin_nan("");
 }
 
 // ---- the product --------------------------------------------------------------------------------------------------
@@ -287,8 +306,12 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
         __syncthreads();                                   // ... and so have everybody else's
     }
 
-    // epilogue: levels -> float64 -> one rounding to float32; column statistics from the float64 values
-    const double kscale = ksc[bb];
+    // epilogue: levels -> float64 -> one rounding to float32; column statistics from the float64 values.  The digit scale of
+    // Kzx: the build's slot of k-block 0 for these columns, NaN if the slot of any k-block this tile read is NaN
+    const int64_t gx = (np + 255) >> 8;
+    const double* ks = ksc + bb * KB * gx + (n0 >> 8);
+    const double kslot = tid < nkb ? ks[(int64_t)tid * gx] : 0.0;
+    const double kscale = __syncthreads_or(kslot != kslot) ? __builtin_nan("") : ks[0];
     double sdot = 0.0, ssq = 0.0;
     const int64_t col = n0 + wn0 + lr;
     const float* rvb = rv ? rv + bb * M : nullptr;
@@ -344,6 +367,9 @@ size_t nsgp_i8_k_planes_bytes(int64_t batch, int64_t M, int64_t n, int planes) {
     return (batch > 0 && M > 0 && n > 0 && (planes == 4 || planes == 5)) ? (size_t)(batch * planes * i8_kb(M) * 2 * i8_np(n) * 16) : 0;
 }
 size_t nsgp_i8_tiles(int64_t M) { return M > 0 ? (size_t)cdiv64(M, I8_BM) : 0; }
+size_t nsgp_i8_kscale_count(int64_t batch, int64_t M, int64_t n) {                // one slot per build workgroup
+    return (batch > 0 && M > 0 && n > 0) ? (size_t)(batch * i8_kb(M) * cdiv64(i8_np(n), 256)) : 0;
+}
 
 int nsgp_i8_slice_w_f64(const double* W, int64_t batch, int64_t M, void* Wd, double* wscale, void* stream) {
     if (!W) return -1; if (batch < 0) return -2; if (M < 0 || !nsgp_i8_supported(M > 0 ? M : 1)) return -3;

@@ -624,7 +624,7 @@ def _project_a_i8(W64f, kZ, kx, kls, kos, m, A, part_dot, part_sq, T, p64, plane
     Wd = torch.empty(int(lib.nsgp_i8_w_planes_bytes(batch, M)), dtype=torch.uint8, device=dev)
     Kd = torch.empty(int(lib.nsgp_i8_k_planes_bytes(batch, M, n, planes)), dtype=torch.uint8, device=dev)
     wsc = torch.empty((batch, M), dtype=torch.float64, device=dev)
-    ksc = torch.empty((batch,), dtype=torch.float64, device=dev)
+    ksc = torch.empty((int(lib.nsgp_i8_kscale_count(batch, M, n)),), dtype=torch.float64, device=dev)
     K32 = torch.empty((batch, M, n), dtype=torch.float32, device=dev) if kzx_out is not None else None
     _lib.call('nsgp_i8_slice_w_f64', _p(W64f), batch, M, _p(Wd), _p(wsc), st)
     _lib.call('nsgp_i8_rbf_build_f32', _p(kZ), _p(kx), n * D if kx.dim() == 3 else 0, _p(kls), _p(kos), batch, M, n, D,

@@ -105,6 +105,9 @@ def test_round3_entry_points_validate_their_arguments_on_the_host():
     assert lib.nsgp_i8_w_planes_bytes(2, 1024) == 2 * 5 * 32 * 2 * 1024 * 16
     assert lib.nsgp_i8_k_planes_bytes(1, 1024, 4096, 4) == 4 * 32 * 2 * 4096 * 16
     assert lib.nsgp_i8_k_planes_bytes(1, 1024, 4096, 3) == 0                     # only 4 or 5 planes exist
+    # one digit-scale slot per build workgroup (32-deep k-block x 256 columns of the 64-padded n)
+    assert lib.nsgp_i8_kscale_count(2, 1024, 4096) == 2 * 32 * 16 and lib.nsgp_i8_kscale_count(1, 33, 65) == 2 * 1
+    assert lib.nsgp_i8_kscale_count(1, 1024, 0) == 0
     # slicing W
     assert lib.nsgp_i8_slice_w_f64(None, 1, 128, b, b, None) == -1
     assert lib.nsgp_i8_slice_w_f64(b, -1, 128, b, b, None) == -2

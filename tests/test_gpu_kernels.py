@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from conftest import measured
+
 pytestmark = pytest.mark.gpu
 
 F32, F64 = torch.float32, torch.float64
@@ -691,3 +693,90 @@ def test_potrf_trtri_w32_variant_writes_the_rounded_inverse(ops, n, batch):
         assert bool((torch.triu(X32, 1) == 0).all()) and bool((torch.triu(X, 1) == 0).all())
     X0, info0 = ops.potrf_trtri_(K.clone())
     assert torch.equal(torch.tril(X0), torch.tril(X))
+
+
+# ------------------------------------------------------------------------------- Gibbs build + Cholesky at the timed sizes
+def _frob_residual(L, A):
+    """||L L^T - A||_F / ||A||_F with L L^T formed in float64 on the device, 2048-row slabs at a time (at N = 16384 a float64
+    matrix is 2 GB: the slabs keep the footprint at A, L and one float64 copy of L)."""
+    n = A.shape[-1]
+    L64 = L if L.dtype == F64 else L.double()
+    num = den = 0.0
+    for r0 in range(0, n, 2048):
+        r1 = min(n, r0 + 2048)
+        R = L64[r0:r1, :r1] @ L64[:r1, :r1].T - A[r0:r1, :r1].double()
+        num += 2.0 * float((R[:, :r0] ** 2).sum()) + float((R[:, r0:] ** 2).sum())      # the strict lower part twice
+        Ad = A[r0:r1, :r1].double()
+        den += 2.0 * float((Ad[:, :r0] ** 2).sum()) + float((Ad[:, r0:] ** 2).sum())
+        del R, Ad
+    del L64
+    return math.sqrt(num / den)
+
+
+# ||L L^T - A||_F / ||A||_F, ~3x what MI355X measured (float32: 6.0e-7 at 4096, 3.7e-7 at 16384; float64: 1.3e-15, 2.4e-15),
+# far below n u (2.4e-4 / 9.8e-4 float32, 4.5e-13 / 1.8e-12 float64)
+_TIMED_RESIDUAL_TOL = {(4096, F32): 1.8e-6, (16384, F32): 1.2e-6, (4096, F64): 4e-15, (16384, F64): 7.5e-15}
+
+
+@pytest.mark.parametrize('dt', [F32, F64])
+@pytest.mark.parametrize('n', [4096, 16384])
+def test_gibbs_build_and_potrf_at_the_timed_sizes(ops, n, dt):
+    """bench.py --full times the Gibbs build + potrf of sigma_f^2 K + sigma^2 I at N = 4096 and 16384 in both dtypes
+    (bench._b2_inputs): the build against the textbook oracle (symmetry, the diagonal os + noise, 10^4 sampled entries
+    against oracle.kernels.gibbs_scalar), the factor against A (info 0, a zero strict upper triangle, the float64
+    residual ||L L^T - A||_F / ||A||_F) -- float32 at N >= 2048 is where the two-level panel path runs."""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    from oracle import kernels as OK
+    os_v, nz_v = 0.644, 0.011
+    x, e = bench._b2_inputs(n, 'cuda', dt)
+    K = ops.gibbs_build(x, x, e, e, os_v, nz_v)
+    u = 2.0 ** -24 if dt == F32 else 2.0 ** -53
+    # symmetry: the (i, j) and (j, i) entries come from the same formula with the arguments swapped
+    asym = 0.0
+    for r0 in range(0, n, 4096):
+        blk = K[r0:r0 + 4096]
+        asym = max(asym, float((blk - K[:, r0:r0 + 4096].T).abs().max()))
+    kmax = float(K.abs().max())
+    print(f'[measured] gibbs N={n} {dt}: max|K - K^T| {asym:.3g} (max|K| {kmax:.3g})')
+    assert asym <= 4 * u * kmax
+    # the diagonal: Gibbs(x, x) = 1 up to the rounding of its prefactor, so os + noise (measured 7 u float32, 6 u float64)
+    dg = torch.diagonal(K).double().cpu()
+    assert measured(f'gibbs N={n} {dt} diagonal', dg, torch.full_like(dg, os_v + nz_v), rtol=16 * u, atol=0.0)
+    # 10^4 sampled entries (100 of them on the diagonal) against the textbook formula in float64 from the same inputs
+    g = _g(n + (1 if dt == F32 else 2))
+    ii = torch.randint(0, n, (10000,), generator=g)
+    jj = torch.randint(0, n, (10000,), generator=g)
+    jj[:100] = ii[:100]
+    xc, ec = x.double().cpu(), e.double().cpu()
+    Ks = K[ii.cuda(), jj.cuda()].double().cpu()
+    ref = torch.tensor([os_v * OK.gibbs_scalar(xc, xc, ec, ec, int(i), int(j)) + (nz_v if int(i) == int(j) else 0.0)
+                        for i, j in zip(ii.tolist(), jj.tolist())], dtype=F64)
+    # measured max|diff| 2.1e-7 (float32) / 3.3e-16 (float64) at max|K| 0.655; float32's worst relative error (1.2e-6, on a
+    # small entry: exp of a large argument) sets its rtol
+    assert measured(f'gibbs N={n} {dt} sampled entries', Ks, ref, rtol=4e-6 if dt == F32 else 4e-15,
+                    atol=1e-9 if dt == F32 else 1e-17)
+    del Ks, xc, ec
+    L, info = ops.potrf(K)
+    assert int(info.max().item()) == 0 and int(info.min().item()) == 0
+    up = 0.0
+    for r0 in range(0, n, 4096):
+        up = max(up, float(torch.triu(L[r0:r0 + 4096], diagonal=r0 + 1).abs().max()))
+    assert up == 0.0                                          # strict upper triangle exactly zero
+    res = _frob_residual(L, K)
+    tol = _TIMED_RESIDUAL_TOL[(n, dt)]
+    print(f'[measured] potrf N={n} {dt}: ||L L^T - A||_F / ||A||_F = {res:.3g} (bound {tol:.3g}; n u = {n * u:.3g})')
+    assert res < tol
+    if dt == F32 and n == 4096:                               # the factor itself against a float64 Cholesky of the same A
+        Lr = torch.linalg.cholesky(K.double().cpu())
+        err = float((L.double().cpu() - Lr).abs().max() / Lr.abs().max())
+        print(f'[measured] potrf N={n} float32 L vs float64 cholesky: max|dL| / max|L| = {err:.3g}')
+        assert err < F32_CHOL_4096_TOL
+    del L, K
+
+
+F32_CHOL_4096_TOL = 1e-4          # measured 3.1e-5 (max-norm, relative to max|L|)

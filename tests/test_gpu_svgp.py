@@ -217,6 +217,31 @@ def test_non_positive_definite_kzz_is_reported_when_asked():
         assert int(info[0]) == 0
 
 
+@pytest.mark.parametrize('i8', [True, False])
+@pytest.mark.parametrize('fp', ['f32', 'bf16', 'bf16_all'])
+def test_non_positive_definite_kzz_gives_nan_marginals(fp, i8):
+    """The case above through svgp_marginal, on every forward path a float32 layer can select (int8 digit-plane or
+    float64-accumulating A = W Kzx, float32 / bf16 / all-bf16 projections): the NaNs the failed Cholesky leaves in W
+    must reach the mean and the variance -- settings.check_variational_cholesky promises that a non-PD Kzz shows up as
+    NaN downstream when the check is off."""
+    if not torch.cuda.is_available():
+        pytest.skip('no GPU')
+    from nsgp.gp import settings
+    from nsgp.svgp import svgp_marginal
+    M, n = 72, 200                                           # (bf16 projections: M a multiple of 8)
+    Z = torch.randn(1, M, 2, dtype=F32, generator=_g(5)).cuda()
+    x = torch.randn(n, 2, dtype=F32, generator=_g(6)).cuda()
+    ls = torch.ones(1, 2, device='cuda')
+    os_ = -torch.ones(1, device='cuda')
+    m = torch.randn(1, M, generator=_g(7)).cuda()
+    Lq = (torch.tril(0.1 * torch.randn(1, M, M, generator=_g(8))) + torch.eye(M)).cuda()
+    with settings.whiten_matmul_i8(i8), settings.forward_precision(fp):
+        mean, var, info = svgp_marginal(x, Z, ls, os_, m, Lq, jitter=0.0)
+    assert int(info[0]) == 1
+    assert not torch.isfinite(mean).any() and not torch.isfinite(var).any(), (fp, i8, int(torch.isfinite(mean).sum()),
+                                                                            int(torch.isfinite(var).sum()))
+
+
 @pytest.mark.parametrize('M,n,batch,D,shared_x', [(256, 512, 2, 3, True), (1024, 4096, 1, 2, True), (128, 128, 3, 4, False),
                                                    (1024, 640, 2, 1, True)])
 def test_projection_with_generated_kzx_equals_the_materialised_one(M, n, batch, D, shared_x):
