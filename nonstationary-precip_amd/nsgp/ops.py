@@ -9,6 +9,8 @@ Raw ops (no autograd) are lower-case functions returning new tensors; autograd e
 `ps2d_kernel`, `matmul`, `chol_inv`, ...).
 """
 import ctypes
+import functools
+from typing import NamedTuple
 
 import torch
 
@@ -581,8 +583,10 @@ def _timed(launch, flops, dtype):
 
 
 def _affine_args(affine, batch, n, ref):
-    """(x, w, c) of an affine prior mean -> pointer / stride arguments of the *_affine entry points.
+    """(x, w, c) of an affine prior mean -> pointer / stride arguments of the *_affine entry points (all null for None).
     x:(n,D) shared by the batch or (batch,n,D); w:(D,) shared or (batch,D) or None; c:(1,) shared or (batch,) or None."""
+    if affine is None:
+        return None, 0, 0, None, 0, None, 0
     x, w, c = affine
     x = _c(x)
     D = x.shape[-1]
@@ -602,6 +606,20 @@ def _affine_args(affine, batch, n, ref):
         scb = 1 if (c.shape[0] == batch and batch > 1) else 0
     _chk(ref, x, *[t for t in (w, c) if t is not None])
     return x, sxb, D, w, swb, c, scb
+
+
+def _kernel_inputs_args(t, ref, what):
+    """(Z, x, ls, os) of an RBF kernel whose Kzx a projection evaluates itself -> the four tensors contiguous (os flat) and
+    (b, M, n), checked: ref's device and dtype, Z:(b,M,D), x:(n,D) or (b,n,D), ls:(b,D), os:(b,)."""
+    if not isinstance(t, (tuple, list)) or len(t) != 4 or not all(isinstance(v, torch.Tensor) for v in t):
+        raise BackendError(f'{what}: (Z, x, ls, os) expected')
+    _chk(ref, *t)
+    kZ, kx, kls, kos = _c(t[0]), _c(t[1]), _c(t[2]), _c(t[3].reshape(-1))
+    b, D = kZ.shape[0], kZ.shape[-1]
+    if kZ.dim() != 3 or kx.dim() not in (2, 3) or kx.shape[-1] != D or (kx.dim() == 3 and kx.shape[0] != b) \
+            or kls.shape != (b, D) or kos.shape != (b,):
+        raise BackendError(f'{what}: (Z, x, ls, os) shapes')
+    return (kZ, kx, kls, kos), (b, kZ.shape[1], kx.shape[-2])
 
 
 def svgp_kzx_fusable(W64f, Z, x, n):
@@ -635,6 +653,107 @@ def _project_a_i8(W64f, kZ, kx, kls, kos, m, A, part_dot, part_sq, T, p64, plane
                              _p(A), _p(part_dot), _p(part_sq), T, 1 if p64 else 0, st), flops, 'i8')
 
 
+class ProjectionPlan(NamedTuple):
+    """What one forward projection launches and how its column-statistic partials are laid out (`svgp_projection_plan`)."""
+    first: str                  # arithmetic of A = W Kzx: 'f32' | 'f64acc' | 'f64acc_b64' | 'kzx_fused' | 'i8' | 'bf16'
+    second: str                 # arithmetic of C = Lq^T A: 'f32' | 'f64acc_t' | 'bf16'
+    planes: int                 # Kzx digit planes of the int8 product (4 or 5), else 0
+    p1: str                     # entry points: product 1, product 2, and the reduction of the partials to mean and var
+    p2: str
+    fin: str
+    T1: int                     # tile rows product 1 writes (planes 0 and 1 of the partials), product 2 writes (plane 2),
+    T2: int                     # and T of the partials buffer (3, batch, T, n)
+    T: int
+    part_dtype: torch.dtype
+    zero: bool                  # the buffer starts zero-filled
+    scratch: bool               # product 2 writes a compact (batch, T2, n) buffer that is then copied into plane 2
+
+
+@functools.lru_cache(maxsize=None)
+def svgp_projection_plan(M, n, batch, dtype, first, second, i8_planes=4):
+    """The plan of a forward projection, from sizes only (host-side planner queries of the library; no tensor, no GPU).
+    Every kernel lays its partials out by its own tile height -- e.g. M = 1024, n = 4032, b = 1: 8 tile rows in the float32
+    plan, 16 in the float64-accumulating kernel (64-row tiles when its 128-row grid is under one round of the chip) -- so
+    the buffer has T = max(T1, T2) rows and is ZERO-FILLED EXACTLY WHEN SOME ROW OF SOME PLANE IS WRITTEN BY NO KERNEL
+    (T1 < T or T2 < T): finalize sums all T rows of all three planes, and no error code reports an uninitialised one.
+    'f64acc_t' (C accumulated in float64, float64 partials) follows a first product that can write float64 partials."""
+    f32 = dtype == torch.float32
+    if (not f32 and (dtype, first, second) != (torch.float64, 'f32', 'f32')) or (second == 'bf16' and M % 8) \
+            or first not in ('f32', 'f64acc', 'f64acc_b64', 'kzx_fused', 'i8', 'bf16') or (first == 'bf16' and second != 'bf16') \
+            or second not in ('f32', 'f64acc_t', 'bf16') or (second == 'f64acc_t' and first not in ('f64acc_b64', 'i8')):
+        raise BackendError(f'svgp_projection_plan: no {first} / {second} projection of a {dtype} layer with M = {M}')
+    lib, sfx, pre = _lib.load(), 'f32' if f32 else 'f64', 'nsgp_svgp_tri_gemm_colstats_'
+    Tf = int(lib.nsgp_svgp_colstats_tiles(M, n, batch, 4 if f32 else 8))
+    T1, T2 = (int(Tf if a == 'f32' else lib.nsgp_i8_tiles(M) if a == 'i8' else lib.nsgp_svgp_bf16_tiles(M) if a == 'bf16'
+                  else lib.nsgp_svgp_f64acc_tiles_for(M, n, batch)) for a in (first, second))
+    T, p64 = max(T1, T2), second == 'f64acc_t'
+    # the plain float32 / float64 kernel lays its partials out with its own Tf rows; its *_rows twin takes the row count
+    p1 = {'f32': pre + ('' if T == Tf else 'rows_') + sfx, 'f64acc_b64': pre + ('f64acc_b64' if p64 else 'f64acc_b64p32'),
+          'kzx_fused': 'nsgp_svgp_kzx_gemm_colstats_f64acc'}.get(first, pre + first)
+    # int8 with float64 partials has always been zero-filled, also where both kernels report the same tile rows (the
+    # headline's first layer: 8 and 8) and the rule does not ask for it: kept, the launch sequence stays what it was
+    zero = T1 < T or T2 < T or (first == 'i8' and p64)
+    return ProjectionPlan(first, second, (5 if i8_planes == 5 else 4) if first == 'i8' else 0, p1,
+                          pre + ('rows_' + sfx if second == 'f32' else second),
+                          'nsgp_svgp_colstats_finalize_affine_' + ('p64_f32' if p64 else sfx), T1, T2, T,
+                          torch.float64 if p64 else dtype, zero,
+                          second == 'bf16' and T2 != T)       # the bf16 kernel writes its partials with its own row count
+
+
+def _run_projection(plan, dims, W, B, kin, Lq, m, base, base_add, affine, kzx_out=None):
+    """Allocate A, C, the partials, mean and var and launch what `plan` says: product 1 (W: its triangular operand in the
+    precision the plan's arithmetic reads, B: the Kzx it reads or None, kin: the checked (Z, x, ls, os) it evaluates Kzx
+    from or None), the bf16 cast / transpose, product 2 (Lq likewise) and finalize.  Returns A, C, mean, var."""
+    (batch, M, n), dt, dev, st, T = dims, m.dtype, m.device, _stream(), plan.T
+    flops = 1.0 * M * M * n * batch                      # 2 M M n / 2 (triangular operand)
+    A = torch.empty((batch, M, n), dtype=dt, device=dev)
+    C = torch.empty_like(A)
+    part = (torch.zeros if plan.zero else torch.empty)((3, batch, max(T, 1), n), dtype=plan.part_dtype, device=dev)
+    p0, p1 = _p(part[0]), _p(part[1])
+    if kin is not None:
+        kZ, kx, kls, kos = kin
+        D = kZ.shape[-1]
+        sx = n * D if kx.dim() == 3 else 0
+    if plan.second == 'bf16':
+        Ub = torch.empty((batch, M, M), dtype=torch.bfloat16, device=dev)
+        AT = torch.empty((batch, n, M), dtype=torch.bfloat16, device=dev)
+        _lib.call('nsgp_cast_sq_bf16_f32', _p(Lq), _p(Ub), M, batch, 1, 1, st)          # tril(Lq)^T
+    if plan.first == 'f32':
+        rows = (T,) if plan.p1.startswith('nsgp_svgp_tri_gemm_colstats_rows') else ()
+        _timed(lambda: _lib.call(plan.p1, _p(W), 0, _p(B), _p(m), batch, M, n, _p(A), p0, p1, *rows, st), flops, dt)
+    elif plan.first in ('f64acc', 'f64acc_b64'):
+        _timed(lambda: _lib.call(plan.p1, _p(W), _p(B), _p(m), batch, M, n, _p(A), p0, p1, T, st), flops, 'f64acc')
+    elif plan.first == 'kzx_fused':
+        _timed(lambda: _lib.call(plan.p1, _p(W), _p(kZ), _p(kx), sx, _p(kls), _p(kos), D, _p(m), batch, M, n, _p(A), p0, p1,
+                                 T, st), flops, 'f64acc')
+    elif plan.first == 'i8':
+        _project_a_i8(W, kZ, kx, kls, kos, m, A, part[0], part[1], T, plan.part_dtype != dt, plan.planes, flops,
+                      kzx_out=kzx_out)
+    else:                                                # bf16: bf16 copies of W and of Kxz, written by the build kernel
+        Wb = torch.empty((batch, M, M), dtype=torch.bfloat16, device=dev)
+        Kxz = torch.empty((batch, n, M), dtype=torch.bfloat16, device=dev)
+        _lib.call('nsgp_cast_sq_bf16_f64' if W.dtype == torch.float64 else 'nsgp_cast_sq_bf16_f32', _p(W), _p(Wb), M, batch,
+                  0, 1, st)
+        _lib.call('nsgp_rbf_build_t_bf16', _p(kZ), _p(kx), _p(kls), _p(kos), batch, M, n, D, sx, _p(Kxz), st)
+        _timed(lambda: _lib.call(plan.p1, _p(Wb), 1, _p(Kxz), _p(m), batch, M, n, _p(A), _p(AT), p0, p1, st), flops, 'bf16')
+    if plan.second == 'f32':
+        _timed(lambda: _lib.call(plan.p2, _p(Lq), 1, _p(A), None, batch, M, n, _p(C), None, _p(part[2]), T, st), flops, dt)
+    elif plan.second == 'f64acc_t':                      # C = Lq^T A accumulated in float64 (layers that feed the next layer)
+        _timed(lambda: _lib.call(plan.p2, _p(Lq), _p(A), batch, M, n, _p(C), _p(part[2]), T, st), flops, 'f64acc')
+    else:
+        if plan.first != 'bf16':                         # (the bf16 first product writes the bf16 A^T along)
+            _lib.call('nsgp_transpose_cast_bf16', _p(A), _p(AT), batch, M, n, st)
+        p2 = torch.empty((batch, plan.T2, n), dtype=dt, device=dev) if plan.scratch else part[2]
+        _timed(lambda: _lib.call(plan.p2, _p(Ub), 2, _p(AT), None, batch, M, n, _p(C), None, None, _p(p2), st), flops, 'bf16')
+        if plan.scratch:
+            part[2, :, :plan.T2].copy_(p2)
+    mean, var = torch.empty((batch, n), dtype=dt, device=dev), torch.empty((batch, n), dtype=dt, device=dev)
+    x, sxb, Da, w, swb, c, scb = _affine_args(affine, batch, n, m)
+    _lib.call(plan.fin, _p(part[0]), _p(part[1]), _p(part[2]), _p(base), float(base_add), batch, T, n, _p(x), sxb, Da,
+              _p(w), swb, _p(c), scb, _p(mean), _p(var), st)
+    return A, C, mean, var
+
+
 def svgp_project(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None, kernel_inputs=None, Kzx64=None, Lq64=None,
                  i8_inputs=None, i8_planes=4, i8_kzx_out=None):
     """Fused K6 forward: A = W Kzx, C = Lq^T A (triangular MFMA GEMMs) with the column statistics reduced in
@@ -644,107 +763,43 @@ def svgp_project(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None, kern
     W64f: the float64 W of a float32 layer -- A is then accumulated in float64 on the float32 Kzx and rounded once
     (nsgp_svgp_tri_gemm_colstats_f64acc: the reference's float64 solve); W itself (float32) is only used by the backward.
     kernel_inputs=(Z, x, ls, os) with Kzx=None (and W64f, `svgp_kzx_fusable`): Kzx is never materialised, its tiles are
-    generated inside the loader of the first product from Z:(b,M,D), x:(n,D) or (b,n,D), ls:(b,D), os:(b,)."""
-    i8 = i8_inputs is not None
-    if i8:
-        # A = W Kzx on the int8 matrix cores (csrc/gemm_i8.hip): exact int32 accumulation of 14 digit-plane products of the
-        # float64 W and of Kzx evaluated in float64 from (Z, x, ls, os); Kzx itself is never materialised in the forward pass
-        if Kzx is not None or Kzx64 is not None or kernel_inputs is not None or W64f is None:
-            raise BackendError('svgp_project: i8_inputs=(Z, x, ls, os) comes with W64f and without Kzx / Kzx64 / kernel_inputs')
-        kZ, kx, kls, kos = i8_inputs
-        ref = _chk(W, Lq, m, base, kZ, kx, kls, kos)
-        kZ, kx, kls, kos = _c(kZ), _c(kx), _c(kls), _c(kos.reshape(-1))
-        W, Lq, m, base = _c(W), _c(Lq), _c(m), _c(base.reshape(-1))
-        batch, M, D = kZ.shape
-        n = kx.shape[-2]
-        if ref.dtype != torch.float32 or kx.shape[-1] != D or (kx.dim() == 3 and kx.shape[0] != batch) \
-                or kls.shape != (batch, D) or kos.shape != (batch,) or D > 4 or not _lib.load().nsgp_i8_supported(M):
-            raise BackendError('svgp_project: i8_inputs shapes (float32 layer, D <= 4, M <= 4096)')
-    b64 = Kzx64 is not None
-    if b64:
-        if Kzx is not None or W64f is None or Kzx64.dtype != torch.float64 or Kzx64.dim() != 3:
-            raise BackendError('svgp_project: Kzx64 (float64 (b,M,n), with W64f, instead of Kzx) expected')
-        ref = _chk(W, Lq, m, base)
-        if Kzx64.device != ref.device:
-            raise BackendError('svgp_project: Kzx64 device')
-        W, Kzx64, Lq, m, base = _c(W), _c(Kzx64), _c(Lq), _c(m), _c(base.reshape(-1))
-        batch, M, n = Kzx64.shape
+    generated inside the loader of the first product from Z:(b,M,D), x:(n,D) or (b,n,D), ls:(b,D), os:(b,).
+    Kzx64 (float64 (b,M,n), with W64f, instead of Kzx): the same product on a float64 Kzx.  i8_inputs=(Z, x, ls, os) (with
+    W64f, instead of Kzx): A on the int8 matrix cores (csrc/gemm_i8.hip), exact int32 accumulation of the digit-plane
+    products of the float64 W and of Kzx evaluated in float64 -- 14 with four Kzx planes, 19 with five (`i8_planes`).
+    Lq64 (with Kzx64 or i8_inputs): the float64 Lq -- C is accumulated in float64 too, with float64 partials."""
+    i8, b64 = i8_inputs is not None, Kzx64 is not None
+    if i8 and (Kzx is not None or b64 or kernel_inputs is not None or W64f is None):
+        raise BackendError('svgp_project: i8_inputs=(Z, x, ls, os) comes with W64f and without Kzx / Kzx64 / kernel_inputs')
+    ref = _chk(W, Kzx, Lq, m, base)
+    if b64 and (Kzx is not None or W64f is None or Kzx64.dtype != torch.float64 or Kzx64.dim() != 3 or Kzx64.device != ref.device):
+        raise BackendError('svgp_project: Kzx64 (float64 (b,M,n) on the layer device, with W64f, instead of Kzx) expected')
     fused = Kzx is None and not b64 and not i8
-    if fused:
-        if kernel_inputs is None or W64f is None:
-            raise BackendError('svgp_project: Kzx=None needs kernel_inputs and W64f')
-        kZ, kx, kls, kos = kernel_inputs
-        ref = _chk(W, Lq, m, base, kZ, kx, kls, kos)
-        kZ, kx, kls, kos = _c(kZ), _c(kx), _c(kls), _c(kos.reshape(-1))
-        W, Lq, m, base = _c(W), _c(Lq), _c(m), _c(base.reshape(-1))
-        batch, M, D = kZ.shape
-        n = kx.shape[-2]
-        if kx.shape[-1] != D or (kx.dim() == 3 and kx.shape[0] != batch) or kls.shape != (batch, D) or kos.shape != (batch,):
-            raise BackendError('svgp_project: kernel_inputs shapes')
-    elif not b64 and not i8:
-        ref = _chk(W, Kzx, Lq, m, base)
-        W, Kzx, Lq, m, base = _c(W), _c(Kzx), _c(Lq), _c(m), _c(base.reshape(-1))
-        batch, M, n = Kzx.shape
+    if fused and (kernel_inputs is None or W64f is None):
+        raise BackendError('svgp_project: Kzx=None needs kernel_inputs and W64f')
+    kin = B = None
+    if i8 or fused:
+        kin, (batch, M, n) = _kernel_inputs_args(i8_inputs if i8 else kernel_inputs, ref, 'svgp_project')
+        if i8 and (ref.dtype != torch.float32 or kin[0].shape[2] > 4 or not _lib.load().nsgp_i8_supported(M)):
+            raise BackendError('svgp_project: i8_inputs shapes (float32 layer, D <= 4, M <= 4096)')
+    else:
+        B = _c(Kzx64 if b64 else Kzx)
+        batch, M, n = B.shape
+    W, Lq, m, base = _c(W), _c(Lq), _c(m), _c(base.reshape(-1))
     if W.shape != (batch, M, M) or Lq.shape != (batch, M, M) or m.shape != (batch, M) or base.shape != (batch,):
         raise BackendError('svgp_project: shapes')
-    lib = _lib.load()
-    T = int(lib.nsgp_svgp_colstats_tiles(M, n, batch, ref.element_size()))
-    A = torch.empty((batch, M, n), dtype=ref.dtype, device=ref.device)
-    C = torch.empty_like(A)
-    sfx, st = _sfx(ref), _stream()
-    flops = 1.0 * M * M * n * batch                      # 2 M M n / 2 (triangular operand)
     if W64f is not None:
         if ref.dtype != torch.float32 or W64f.dtype != torch.float64 or W64f.shape != (batch, M, M) \
                 or W64f.device != ref.device:
             raise BackendError('svgp_project: W64f must be the float64 (b,M,M) W of a float32 layer')
-        W64f = _c(W64f)
-        T64 = int(lib.nsgp_i8_tiles(M)) if i8 else int(lib.nsgp_svgp_f64acc_tiles_for(M, n, batch))   # tile rows of product 1
-        if i8 and Lq64 is not None:               # product 2 on the float64-accumulating kernel: ITS tile rows for part[2]
-            T64 = max(T64, int(lib.nsgp_svgp_f64acc_tiles_for(M, n, batch)))
-        p64 = (b64 or i8) and Lq64 is not None    # both projections accumulate in float64: float64 partials
-        T32, T = T, (T64 if p64 else max(T, T64))
-        # tile rows one of the two kernels does not fill (their tile heights differ for some shapes) stay zero
-        part = (torch.zeros if ((T64 != T32 and not p64) or (i8 and p64)) else torch.empty)(
-            (3, batch, max(T, 1), n), dtype=torch.float64 if p64 else ref.dtype, device=ref.device)
-        if i8:
-            _project_a_i8(W64f, kZ, kx, kls, kos, m, A, part[0], part[1], T, p64, 5 if i8_planes == 5 else 4, flops,
-                          kzx_out=i8_kzx_out)
-        elif b64 and p64:
-            _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_f64acc_b64', _p(W64f), _p(Kzx64), _p(m), batch, M, n, _p(A),
-                                     _p(part[0]), _p(part[1]), T, st), flops, 'f64acc')
-        elif b64:                                 # float64 Kzx, float32 partials (the second projection stays float32)
-            _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_f64acc_b64p32', _p(W64f), _p(Kzx64), _p(m), batch, M, n, _p(A),
-                                     _p(part[0]), _p(part[1]), T, st), flops, 'f64acc')
-        elif fused:
-            _timed(lambda: _lib.call('nsgp_svgp_kzx_gemm_colstats_f64acc', _p(W64f), _p(kZ), _p(kx),
-                                     n * D if kx.dim() == 3 else 0, _p(kls), _p(kos), D, _p(m), batch, M, n, _p(A),
-                                     _p(part[0]), _p(part[1]), T, st), flops, 'f64acc')
-        else:
-            _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_f64acc', _p(W64f), _p(Kzx), _p(m), batch, M, n, _p(A),
-                                     _p(part[0]), _p(part[1]), T, st), flops, 'f64acc')
-    else:
-        part = torch.empty((3, batch, max(T, 1), n), dtype=ref.dtype, device=ref.device)
-        _timed(lambda: _lib.call(f'nsgp_svgp_tri_gemm_colstats_{sfx}', _p(W), 0, _p(Kzx), _p(m), batch, M, n, _p(A),
-                                 _p(part[0]), _p(part[1]), st), flops, ref.dtype)
-    if Lq64 is not None:                      # C = Lq^T A accumulated in float64 (layers that feed the next layer)
+        W = _c(W64f)
+    if Lq64 is not None:
         if W64f is None or not (b64 or i8) or Lq64.dtype != torch.float64 or Lq64.shape != (batch, M, M) or Lq64.device != ref.device:
             raise BackendError('svgp_project: Lq64 must be the float64 (b,M,M) copy of Lq (with W64f and Kzx64 / i8_inputs)')
-        _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_f64acc_t', _p(_c(Lq64)), _p(A), batch, M, n, _p(C), _p(part[2]),
-                                 T, st), flops, 'f64acc')
-    else:
-        _timed(lambda: _lib.call(f'nsgp_svgp_tri_gemm_colstats_rows_{sfx}', _p(Lq), 1, _p(A), None, batch, M, n, _p(C),
-                                 None, _p(part[2]), T, st), flops, ref.dtype)
-    mean = torch.empty((batch, n), dtype=ref.dtype, device=ref.device)
-    var = torch.empty_like(mean)
-    if affine is None:
-        x = w = c = None
-        sxb = D = swb = scb = 0
-    else:
-        x, sxb, D, w, swb, c, scb = _affine_args(affine, batch, n, ref)
-    fin = 'nsgp_svgp_colstats_finalize_affine_p64_f32' if part.dtype != ref.dtype else f'nsgp_svgp_colstats_finalize_affine_{sfx}'
-    _lib.call(fin, _p(part[0]), _p(part[1]), _p(part[2]), _p(base),
-              float(base_add), batch, T, n, _p(x), sxb, D, _p(w), swb, _p(c), scb, _p(mean), _p(var), st)
-    return A, C, mean, var
+        Lq = _c(Lq64)
+    first = 'i8' if i8 else 'f64acc_b64' if b64 else 'kzx_fused' if fused else 'f64acc' if W64f is not None else 'f32'
+    plan = svgp_projection_plan(M, n, batch, ref.dtype, first, 'f32' if Lq64 is None else 'f64acc_t', i8_planes)
+    return _run_projection(plan, (batch, M, n), W, B, kin, Lq, m, base, base_add, affine, i8_kzx_out)
 
 
 def svgp_project_bf16(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None, kernel_inputs=None, i8_inputs=None,
@@ -752,104 +807,35 @@ def svgp_project_bf16(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None,
     """BASELINE configs[4]'s "bf16 forward": the forward projections of a float32 SVGP layer with bf16 matrix-core products
     (bf16 operands, float32 accumulation, float32 A / C; csrc/gemm_bf16.hip), column statistics in the epilogues.
 
-    kernel_inputs=None (settings.forward_precision('bf16')): A = W Kzx runs as in `svgp_project` (float32, or float64
-        accumulation with W64f) -- its terms |W||Kzx| ~ 1e2 cancel to O(1), which bf16 operands cannot carry (measured at
-        M = 2048: 160 % error on the layer outputs) -- and C = Lq^T A, whose operands are O(1), runs on the bf16 cores from a
-        bf16 transposed copy of A.
+    kernel_inputs=None (settings.forward_precision('bf16')): A = W Kzx runs as in `svgp_project` (float32, float64
+        accumulation with W64f, int8 with W64f and i8_inputs, Kzx then optional) -- its terms |W||Kzx| ~ 1e2 cancel to O(1),
+        which bf16 operands cannot carry (measured at M = 2048: 160 % error on the layer outputs) -- and C = Lq^T A, whose
+        operands are O(1), runs on the bf16 cores from a bf16 transposed copy of A.
     kernel_inputs=(Z, x, ls, os) (forward_precision('bf16_all')): BOTH products in bf16, Kxz written in bf16 by the build
         kernel (nsgp_rbf_build_t_bf16) -- configs[4] to the letter; a throughput figure, not a usable numerical mode.
     Returns A, C, mean, var (float32).  M must be a multiple of 8."""
     ref = _chk(Lq, m, base, Kzx)
     if ref.dtype != torch.float32:
         raise BackendError('svgp_project_bf16: float32 layers only')
-    Lq, m, base = _c(Lq), _c(m), _c(base.reshape(-1))
-    if Kzx is None:                          # mode 'bf16' with product 1 on the int8 cores: Kzx is never materialised
-        if i8_inputs is None or W64f is None or kernel_inputs is not None:
-            raise BackendError('svgp_project_bf16: Kzx=None needs i8_inputs and W64f (mode bf16)')
-        batch, M = i8_inputs[0].shape[0], i8_inputs[0].shape[1]
-        n = i8_inputs[1].shape[-2]
-    else:
-        Kzx = _c(Kzx)
-        batch, M, n = Kzx.shape
+    if Kzx is None and (i8_inputs is None or W64f is None or kernel_inputs is not None):
+        raise BackendError('svgp_project_bf16: Kzx=None needs i8_inputs and W64f (mode bf16)')
+    first = 'bf16' if kernel_inputs is not None else 'f32' if W64f is None else 'f64acc' if i8_inputs is None else 'i8'
+    kin = dims = None
+    if first in ('bf16', 'i8'):
+        kin, dims = _kernel_inputs_args(kernel_inputs if first == 'bf16' else i8_inputs, ref, 'svgp_project_bf16')
+    if Kzx is not None:
+        Kzx, kdims = _c(Kzx), dims
+        dims = tuple(Kzx.shape)
+    batch, M, n = dims
     if M % 8 != 0:
         raise BackendError('svgp_project_bf16: M must be a multiple of 8')
-    if Lq.shape != (batch, M, M) or m.shape != (batch, M) or base.shape != (batch,):
+    Lq, m, base = _c(Lq), _c(m), _c(base.reshape(-1))
+    if Lq.shape != (batch, M, M) or m.shape != (batch, M) or base.shape != (batch,) \
+            or (Kzx is not None and kdims not in (None, dims)):          # (Z, x, ls, os) of another size than Kzx
         raise BackendError('svgp_project_bf16: shapes')
-    lib = _lib.load()
-    st = _stream()
-    bf = torch.bfloat16
-    Ub = torch.empty((batch, M, M), dtype=bf, device=ref.device)
-    AT = torch.empty((batch, n, M), dtype=bf, device=ref.device)
-    _lib.call('nsgp_cast_sq_bf16_f32', _p(Lq), _p(Ub), M, batch, 1, 1, st)          # tril(Lq)^T
-    T = int(lib.nsgp_svgp_bf16_tiles(M))                                              # 128-row tiles
-    C = torch.empty((batch, M, n), dtype=ref.dtype, device=ref.device)
-    flops = 1.0 * M * M * n * batch
-    if kernel_inputs is None:
-        # product 1 at full precision.  Its partials are laid out with ITS kernel's tile rows: the float32 plan's (Tf), or
-        # the float64-accumulating kernel's (T64: 128-row tiles, 64-row ones when the 128-row grid is under one round --
-        # e.g. M = 1024, n = 4032, b = 1 gives Tf = 8 but T64 = 16).  One buffer with the largest count; rows a kernel does
-        # not fill stay zero, exactly as in svgp_project.
-        Tf = int(lib.nsgp_svgp_colstats_tiles(M, n, batch, 4))
-        use_i8 = i8_inputs is not None and W64f is not None
-        T64 = (int(lib.nsgp_i8_tiles(M)) if use_i8 else int(lib.nsgp_svgp_f64acc_tiles_for(M, n, batch))) if W64f is not None else Tf
-        T1 = T64 if W64f is not None else Tf                       # tile rows product 1 writes
-        Tp = max(T1, T)
-        A = torch.empty((batch, M, n), dtype=ref.dtype, device=ref.device)
-        part = (torch.zeros if (T1 != Tp or T != Tp) else torch.empty)((3, batch, max(Tp, 1), n), dtype=ref.dtype,
-                                                                       device=ref.device)
-        W = _c(W)
-        if use_i8:
-            kZ, kx, kls, kos = i8_inputs
-            _project_a_i8(_c(W64f), _c(kZ), _c(kx), _c(kls), _c(kos.reshape(-1)), m, A, part[0], part[1], Tp, False, 4, flops,
-                          kzx_out=i8_kzx_out)
-        elif W64f is not None:
-            _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_f64acc', _p(_c(W64f)), _p(Kzx), _p(m), batch, M, n, _p(A),
-                                     _p(part[0]), _p(part[1]), Tp, st), flops, 'f64acc')
-        elif Tp == Tf:
-            _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_f32', _p(W), 0, _p(Kzx), _p(m), batch, M, n, _p(A),
-                                     _p(part[0]), _p(part[1]), st), flops, ref.dtype)
-        else:
-            _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_rows_f32', _p(W), 0, _p(Kzx), _p(m), batch, M, n, _p(A),
-                                     _p(part[0]), _p(part[1]), Tp, st), flops, ref.dtype)
-        _lib.call('nsgp_transpose_cast_bf16', _p(A), _p(AT), batch, M, n, st)
-        if Tp != T:
-            # the bf16 kernel lays its partials out with its own tile-row count: give it a compact buffer, then widen
-            p2 = torch.empty((batch, T, n), dtype=ref.dtype, device=ref.device)
-            _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_bf16', _p(Ub), 2, _p(AT), None, batch, M, n, _p(C), None,
-                                     None, _p(p2), st), flops, 'bf16')
-            part[2, :, :T].copy_(p2)
-        else:
-            _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_bf16', _p(Ub), 2, _p(AT), None, batch, M, n, _p(C), None,
-                                     None, _p(part[2]), st), flops, 'bf16')
-        T = Tp
-    else:
-        Z, x, ls, os_ = kernel_inputs
-        Z, ls, os_ = _c(Z), _c(ls), _c(os_.reshape(-1))
-        D = Z.shape[-1]
-        x = _c(x)
-        sxb = 0 if x.dim() == 2 else x.shape[1] * D
-        Wsrc = _c(W64f) if W64f is not None else _c(W)
-        Wb = torch.empty((batch, M, M), dtype=bf, device=ref.device)
-        Kxz = torch.empty((batch, n, M), dtype=bf, device=ref.device)
-        _lib.call('nsgp_cast_sq_bf16_f64' if Wsrc.dtype == torch.float64 else 'nsgp_cast_sq_bf16_f32', _p(Wsrc), _p(Wb), M,
-                  batch, 0, 1, st)
-        _lib.call('nsgp_rbf_build_t_bf16', _p(Z), _p(x), _p(ls), _p(os_), batch, M, n, D, sxb, _p(Kxz), st)
-        part = torch.empty((3, batch, max(T, 1), n), dtype=ref.dtype, device=ref.device)
-        A = torch.empty_like(Kzx)
-        _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_bf16', _p(Wb), 1, _p(Kxz), _p(m), batch, M, n, _p(A), _p(AT),
-                                 _p(part[0]), _p(part[1]), st), flops, 'bf16')
-        _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_bf16', _p(Ub), 2, _p(AT), None, batch, M, n, _p(C), None,
-                                 None, _p(part[2]), st), flops, 'bf16')
-    mean = torch.empty((batch, n), dtype=ref.dtype, device=ref.device)
-    var = torch.empty_like(mean)
-    if affine is None:
-        xa = w = c = None
-        sxa = Da = swb = scb = 0
-    else:
-        xa, sxa, Da, w, swb, c, scb = _affine_args(affine, batch, n, ref)
-    _lib.call('nsgp_svgp_colstats_finalize_affine_f32', _p(part[0]), _p(part[1]), _p(part[2]), _p(base), float(base_add),
-              batch, T, n, _p(xa), sxa, Da, _p(w), swb, _p(c), scb, _p(mean), _p(var), st)
-    return A, C, mean, var
+    plan = svgp_projection_plan(M, n, batch, ref.dtype, first, 'bf16')
+    return _run_projection(plan, (batch, M, n), _c(W if W64f is None else W64f), Kzx, kin, Lq, m, base, base_add, affine,
+                           i8_kzx_out)
 
 
 def svgp_project_bwd(Lq, m, A, C, gmean, gvar, affine=None):
@@ -872,11 +858,9 @@ def svgp_project_bwd(Lq, m, A, C, gmean, gvar, affine=None):
     flops = 1.0 * M * M * n * batch
     basebar = torch.empty(batch, dtype=ref.dtype, device=ref.device)
     wbar = cbar = None
-    if affine is None:
-        x, sxb, D, shared = None, 0, 0, 0
-    else:
-        x, sxb, D, w, swb, c, scb = _affine_args(affine, batch, n, ref)
-        shared = int(swb == 0 and scb == 0)
+    x, sxb, D, w, swb, c, scb = _affine_args(affine, batch, n, ref)
+    shared = int(affine is not None and swb == 0 and scb == 0)
+    if affine is not None:
         if w is not None and c is not None and batch > 1 and (swb == 0) != (scb == 0):
             raise BackendError('affine prior mean: weights and constant must both be shared or both be per batch')
         nb = 1 if shared else batch

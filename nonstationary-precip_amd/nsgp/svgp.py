@@ -161,6 +161,38 @@ def whiten(groups, jitter=1e-4, chol_bwd_f64=True, passthrough=False, out_dtype=
     return tuple(out)
 
 
+def select_projection(dtype, M, D, n, kzx_f64, has_w64, fusable, forward_precision, whiten_matmul_f64, whiten_matmul_i8,
+                      fuse_kzx, hidden_var_f64):
+    """Which arithmetic a layer's forward projection runs in, from sizes and the settings' values only: (first, second) in
+    ops.svgp_projection_plan's names, the int8 product's Kzx planes, whether it takes the float64 W.  kzx_f64: the layer
+    feeds the next one (settings.hidden_kzx_f64); has_w64: the float64 W of the whitening chain is at hand; fusable: the
+    generated-Kzx kernel supports the shape.
+    A = W Kzx of a float32 layer with the float64 W (kept under whiten_matmul_f64, and by 'bf16_all' regardless):
+     * fuse_kzx (wins over int8): Kzx never materialised in the forward pass, its tiles are generated inside the loader of
+       the float64-accumulating product (whole tiles); the backward builds it once for Wbar = tril(Abar Kzx^T);
+     * the exact int8 digit-plane product (whiten_matmul_i8; M <= 4096, D <= 4; wins over a float64 Kzx): four Kzx planes /
+       14 plane products (1e-6 of max|A|), five / 19 for a layer that feeds the next one (A to float32 rounding);
+     * int8 off: the float64-accumulating product on the float32 Kzx (round 2) -- on a float64 Kzx, which the forward then
+       builds, for a layer that feeds the next one ('f64acc_b64').
+    C = Lq^T A: float32, except for a layer that feeds the next one and sees at most 8192 points -- the first hidden layer
+    of a deep GP (hidden_var_f64) -- where it accumulates in float64 on a float64 copy of Lq ('f64acc_t') with float64
+    column-statistic partials: the variance os + colsum(C^2 - A^2) cancels to << os once q(u) has trained and reaches the
+    next layer's inputs through sqrt(var) eps.  Measured after 1000 Adam steps at the headline shape (max-norm, vs the
+    float64 oracle; tests/test_gpu_headline_precision.py): output mean 4.4e-6 with it, 5.2e-5 without (the reference's own
+    float32 arithmetic: 4.5e-4); +0.12 ms on a 4.34 ms step.
+    'bf16' (BASELINE configs[4]; float32 layers, M % 8 == 0, else as 'f32'): C on the bf16 cores; 'bf16_all' also A."""
+    fp = forward_precision
+    w64 = dtype == torch.float32 and has_w64 and (whiten_matmul_f64 or fp == 'bf16_all')
+    fuse = fp == 'f32' and fuse_kzx and w64 and fusable
+    i8 = fp in ('f32', 'bf16') and not fuse and w64 and whiten_matmul_i8 and D <= 4 and M <= 4096
+    can64 = kzx_f64 and fp == 'f32' and w64 and not fuse
+    var64 = can64 and ((n <= 8192) if hidden_var_f64 == 'auto' else bool(hidden_var_f64))
+    bf16 = dtype == torch.float32 and fp in ('bf16', 'bf16_all') and M % 8 == 0
+    first = 'bf16' if (bf16 and fp == 'bf16_all') else 'kzx_fused' if fuse else 'i8' if i8 else \
+        'f64acc_b64' if can64 else 'f64acc' if w64 else 'f32'
+    return first, 'bf16' if bf16 else 'f64acc_t' if var64 else 'f32', 5 if (kzx_f64 and not bf16) else 4, bool(w64)
+
+
 class SVGPLayerFn(torch.autograd.Function):
     """(x, Z, ls, os, m, Lq, W64, mean_w, mean_c) -> (mean:(b,n), var:(b,n))
 
@@ -176,60 +208,40 @@ class SVGPLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Z, ls, os_, m, Lq, W64, mean_w, mean_c, W64f=None, kzx_f64=False):
+        from .gp import settings
         W = W64 if W64.dtype == x.dtype else ops.cast(W64, x.dtype)
         if W64f is None and W64.dtype == torch.float64 and x.dtype == torch.float32:
             W64f = W64
-        from .gp import settings
-        if x.dtype != torch.float32 or not (settings.whiten_matmul_f64.on() or settings.forward_precision.value() == 'bf16_all'):
-            W64f = None
+        first, second, planes, w64 = select_projection(
+            x.dtype, Z.shape[-2], Z.shape[-1], x.shape[-2], kzx_f64, W64f is not None,
+            settings.fuse_kzx.on() and ops.svgp_kzx_fusable(W64f, Z, x, x.shape[-2]), settings.forward_precision.value(),
+            settings.whiten_matmul_f64.on(), settings.whiten_matmul_i8.on(), settings.fuse_kzx.on(), settings.hidden_var_f64.value())
+        W64f = W64f if w64 else None
         affine = None if (mean_w is None and mean_c is None) else (x, mean_w, mean_c)
-        fp = settings.forward_precision.value()
-        # Kzx never materialised in the forward pass: its tiles are generated inside the loader of A = W Kzx (float32 layers
-        # with the float64-accumulating product, whole tiles); the backward builds it once for Wbar = tril(Abar Kzx^T)
-        fuse = fp == 'f32' and settings.fuse_kzx.on() and W64f is not None and \
-            ops.svgp_kzx_fusable(W64f, Z, x, x.shape[-2])
-        # Which arithmetic for A = W Kzx (float32 layers with the float64 W of the whitening chain):
-        #  * the exact int8 digit-plane product (settings.whiten_matmul_i8; M <= 4096, D <= 4): four Kzx planes / 14 plane
-        #    products (1e-6 of max|A|), five / 19 for a layer that feeds the next one (kzx_f64: A to float32 rounding);
-        #  * int8 off: the float64-accumulating product on the float32 Kzx (round 2) -- on a float64 Kzx for a layer that
-        #    feeds the next one (settings.hidden_kzx_f64).
-        # And for C = Lq^T A: float32, except for a layer that feeds the next one and sees at most 8192 points -- the first
-        # hidden layer of a deep GP (settings.hidden_var_f64) -- where it accumulates in float64 with float64 column-statistic
-        # partials: the variance os + colsum(C^2 - A^2) cancels to << os once q(u) has trained and reaches the next layer's
-        # inputs through sqrt(var) eps.  Measured after 1000 Adam steps at the headline shape (max-norm, vs the float64
-        # oracle; tests/test_gpu_headline_precision.py): output mean 4.4e-6 with it, 5.2e-5 without (the reference's own
-        # float32 arithmetic: 4.5e-4); +0.12 ms on a 4.34 ms step.
-        Kzx64 = Lq64 = None
-        can64 = kzx_f64 and fp == 'f32' and W64f is not None and not fuse
-        hv = settings.hidden_var_f64.value()
-        var64 = can64 and ((x.shape[-2] <= 8192) if hv == 'auto' else bool(hv))
-        use_i8 = (fp in ('f32', 'bf16') and not fuse and W64f is not None and settings.whiten_matmul_i8.on()
-                  and Z.shape[-1] <= 4 and Z.shape[-2] <= 4096)
-        if can64 and not use_i8:
-            src = [x.detach(), Z.detach(), ls.detach(), os_.detach()] + ([Lq.detach()] if var64 else [])
+        Kzx = Kzx64 = Lq64 = None
+        if first == 'f64acc_b64':
+            src = [x.detach(), Z.detach(), ls.detach(), os_.detach()] + ([Lq.detach()] if second == 'f64acc_t' else [])
             dst = [torch.empty(t.shape, dtype=torch.float64, device=t.device) for t in src]
             torch._foreach_copy_(dst, src)
             Kzx64 = ops.rbf_build(dst[1], dst[0], dst[2], dst[3])
-            Lq64 = dst[4] if var64 else None  # C = Lq^T A accumulates in float64 too (the variance's cancellation)
-        elif var64:
+            Lq64 = dst[4] if len(dst) == 5 else None
+        elif second == 'f64acc_t':
             Lq64 = ops.cast(Lq.detach(), torch.float64)
-        Kzx = None if (fuse or Kzx64 is not None or use_i8) else ops.rbf_build(Z, x, ls, os_)           # (b,M,n)
+        elif first in ('f32', 'f64acc', 'bf16'):       # ('bf16' builds its own bf16 Kxz; it takes this one's shape)
+            Kzx = ops.rbf_build(Z, x, ls, os_)           # (b,M,n)
         # int8 path: the plane-build kernel also writes the float32 Kzx the BACKWARD needs (Wbar = tril(Abar Kzx^T)) when there
         # is going to be one -- its own build launch (28 us at the headline's last layer) disappears
-        kzx_keep = [] if (use_i8 and any(ctx.needs_input_grad)) else None
-        if x.dtype == torch.float32 and fp in ('bf16', 'bf16_all') and Z.shape[-2] % 8 == 0:
-            # BASELINE configs[4]'s "bf16 forward": C = Lq^T A on the bf16 matrix cores; 'bf16_all' also A = W Kzx
+        kin = (Z, x, ls, os_)
+        i8 = dict(i8_inputs=kin, i8_kzx_out=[] if any(ctx.needs_input_grad) else None) if first == 'i8' else {}
+        if second == 'bf16':
             A, C, mean, var = ops.svgp_project_bf16(W, Kzx, Lq, m, os_, base_add=VAR_JITTER, affine=affine, W64f=W64f,
-                                                    kernel_inputs=(Z, x, ls, os_) if fp == 'bf16_all' else None,
-                                                    i8_inputs=(Z, x, ls, os_) if (use_i8 and fp == 'bf16') else None,
-                                                    i8_kzx_out=kzx_keep if (use_i8 and fp == 'bf16') else None)
+                                                    kernel_inputs=kin if first == 'bf16' else None, **i8)
         else:
             A, C, mean, var = ops.svgp_project(W, Kzx, Lq, m, os_, base_add=VAR_JITTER, affine=affine, W64f=W64f,
-                                               kernel_inputs=(Z, x, ls, os_) if fuse else None, Kzx64=Kzx64, Lq64=Lq64,
-                                               i8_inputs=(Z, x, ls, os_) if use_i8 else None,
-                                               i8_planes=5 if kzx_f64 else 4, i8_kzx_out=kzx_keep)      # 2 GEMMs
-        if kzx_keep:
-            Kzx = kzx_keep[0]
+                                               kernel_inputs=kin if first == 'kzx_fused' else None, Kzx64=Kzx64,
+                                               Lq64=Lq64, i8_planes=planes, **i8)                    # 2 GEMMs
+        if i8.get('i8_kzx_out'):
+            Kzx = i8['i8_kzx_out'][0]
         ctx.save_for_backward(x, Z, ls, os_, m, Lq, W, Kzx, A, C, mean_w, mean_c)
         ctx.w_dtype = W64.dtype
         return mean, var
