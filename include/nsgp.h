@@ -96,6 +96,33 @@ int nsgp_rbf_build_bwd_f64(const double* x1, const double* x2, const double* ls,
                            void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K2'' Batched Matern-ARD kernel  K[b,i,j] = os[b] * k_nu(d),  d = |(x1[b,i,:]-x2[b,j,:]) / ls[b,:]|
+ *     nu = nu2 / 2 with nu2 in {1, 3, 5} (any other value: argument 11 invalid), a = sqrt(2 nu):
+ *       nu = 1/2: e^-d    nu = 3/2: (1 + a d) e^-ad    nu = 5/2: (1 + a d + 5/3 d^2) e^-ad
+ *     gpytorch ScaleKernel(MaternKernel(nu, ard)) (reference models/latent_priors.py:106-123,
+ *     experiments/seard_spatial_benchmark.py:15).  Arguments and batching as K2.
+ *     backward: as K2, with the same g_x1 == g_x2 summing mode.  For nu = 1/2 the derivative at d = 0 is taken as 0
+ *     (the symmetric subgradient, the limit of nu = 3/2 and 5/2), so the diagonal of K(x, x) adds no gradient.
+ * ------------------------------------------------------------------------------------------ */
+int nsgp_matern_build_fwd_f32(const float* x1, const float* x2, const float* ls, const float* os,
+                              int64_t batch, int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2,
+                              float diag_add, float* K, int64_t ldk, int64_t sK, void* stream);
+int nsgp_matern_build_fwd_f64(const double* x1, const double* x2, const double* ls, const double* os,
+                              int64_t batch, int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2,
+                              double diag_add, double* K, int64_t ldk, int64_t sK, void* stream);
+size_t nsgp_matern_build_bwd_workspace(int64_t batch, int64_t n1, int64_t n2, int D, int elem_size);
+int nsgp_matern_build_bwd_f32(const float* x1, const float* x2, const float* ls, const float* os,
+                              int64_t batch, int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2,
+                              const float* G, int64_t ldg, int64_t sG,
+                              float* g_x1, float* g_x2, float* g_ls, float* g_os,
+                              void* ws, size_t ws_bytes, void* stream);
+int nsgp_matern_build_bwd_f64(const double* x1, const double* x2, const double* ls, const double* os,
+                              int64_t batch, int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2,
+                              const double* G, int64_t ldg, int64_t sG,
+                              double* g_x1, double* g_x2, double* g_ls, double* g_os,
+                              void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K3  Paciorek-Schervish kernel, D = 2, closed-form 2x2 determinants / inverse
  *     K[i,j] = |S1_i|^(1/4) |S2_j|^(1/4) |(S1_i+S2_j)/2|^(-1/2)
  *              * exp(-d^T ((S1_i+S2_j)/2 + jitter I)^-1 d),   d = x1_i - x2_j

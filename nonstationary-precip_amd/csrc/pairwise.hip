@@ -152,6 +152,116 @@ template <typename T, int D> struct RbfOp {
     }
 };
 
+// K2'' batched Matern-ARD, nu = NU2 / 2 in {1/2, 3/2, 5/2} (a template parameter: uniform per launch, so each entry
+// runs straight-line code with its constants folded; three instantiations per D and type).  Same operands, tiles and
+// batching as RbfOp.  u = (x1 - x2) / ls, s = sum_d u_d^2 (RbfOp's FMA chain), d = sqrt(s), a = sqrt(2 nu):
+//   nu = 1/2:  k = e^-d                          phi = (dk/dd) / d = -e^-d / d, 0 at d = 0
+//   nu = 3/2:  k = (1 + a d) e^-ad               phi = -3 e^-ad
+//   nu = 5/2:  k = (1 + a d + 5/3 s) e^-ad       phi = -5/3 (1 + a d) e^-ad
+// dk/du_d = phi u_d; the accumulators are RbfOp's with phi in place of -k (pass 2 divides by ls).
+// d = 0 for nu = 1/2 is the symmetric subgradient (the limit of the other two): K(x, x)'s diagonal adds no gradient.
+// A NaN coordinate stays NaN (the d == 0 test is false for NaN); far entries are 0 * finite, never inf * 0.
+template <typename T> __device__ __forceinline__ T matern_dist(T s);
+// v_sqrt_f32, 1 ulp
+template <> __device__ __forceinline__ float matern_dist<float>(float s) { return t_fsqrt(s); }
+// s * rsqrt(s) (t_rsqrt: 1 ulp in about 7 instructions, against ~17 for the library sqrt); s = 0 and s below the normal
+// range give 0 (d < 1.5e-154 lengthscales), NaN stays NaN
+template <> __device__ __forceinline__ double matern_dist<double>(double s) {
+    return s < 2.2250738585072014e-308 ? 0.0 : s * t_rsqrt(s);
+}
+// k = poly e with e = e^{-a d}, d >= 0 (poly = 1 for nu = 1/2); returns k, writes e.
+// float: a log2(e) is one constant (one rounding less in front of v_exp_f32).  v_exp_f32 returns no denormals, but
+// poly e stays normal while e is not (poly reaches ~1e4 before k leaves the normal range): below 2^-64, e is formed as
+// 2^64 e^{-ad} and the product rescaled by 2^-64, exactly.
+// double: t_fexp gives the smallest denormal, not 0, below -745; exp(x) rounds to 0 there, so the far tail is 0.
+template <int NU2> struct MaternA;
+template <> struct MaternA<1> { static constexpr double a = 1.0, a_log2e = 1.4426950408889634; };
+template <> struct MaternA<3> { static constexpr double a = 1.7320508075688772, a_log2e = 2.4988211106473432; };
+template <> struct MaternA<5> { static constexpr double a = 2.23606797749979, a_log2e = 3.225964182229561; };
+template <int NU2> __device__ __forceinline__ float matern_poly_exp(float d, float poly, float& e) {
+    const float x = d * -(float)MaternA<NU2>::a_log2e;
+    const bool lo = x < -64.0f;
+    const float e2 = __builtin_amdgcn_exp2f(lo ? x + 64.0f : x);
+    e = lo ? e2 * 0x1p-64f : e2;
+    return lo ? (poly * e2) * 0x1p-64f : poly * e2;
+}
+template <int NU2> __device__ __forceinline__ double matern_poly_exp(double d, double poly, double& e) {
+    const double x = d * -MaternA<NU2>::a;
+    e = x < -745.1332191019412 ? 0.0 : t_fexp(x);              // NaN: false, t_fexp(NaN) = NaN
+    return poly * e;
+}
+
+template <typename T, int D, int NU2> struct MaternOp {
+    static_assert(NU2 == 1 || NU2 == 3 || NU2 == 5, "nu = 1/2, 3/2, 5/2");
+    static constexpr int DM = DimMax<D>::v;
+    static constexpr int NR = DM, NC = DM, NG = DM + 1;
+    static constexpr T A = T(MaternA<NU2>::a);
+    const T *x1, *x2, *ls, *os;           // ls:(batch,D) os:(batch)
+    int64_t n1, n2, sx1, sx2;
+    int Drt;
+    struct P { T x[DM]; };                // pre-divided by the lengthscale
+    __device__ __forceinline__ P row(int64_t b, int64_t i) const {
+        P p;
+#pragma unroll
+        for (int d = 0; d < DM; ++d)
+            p.x[d] = (D || d < Drt) ? x1[b * sx1 + i * Drt + d] / ls[b * Drt + d] : T(0);
+        return p;
+    }
+    __device__ __forceinline__ P col(int64_t b, int64_t j) const {
+        P p;
+#pragma unroll
+        for (int d = 0; d < DM; ++d)
+            p.x[d] = (D || d < Drt) ? x2[b * sx2 + j * Drt + d] / ls[b * Drt + d] : T(0);
+        return p;
+    }
+    __device__ __forceinline__ T sq(const P& r, const P& c) const {
+        T s = T(0);
+#pragma unroll
+        for (int d = 0; d < DM; ++d) {
+            const T df = r.x[d] - c.x[d];
+            s = t_fma(df, df, s);
+        }
+        return s;
+    }
+    // k(d); with phi != nullptr also phi(d) = (dk/dd) / d
+    __device__ __forceinline__ T base(const P& r, const P& c, T* phi = nullptr) const {
+        const T s = sq(r, c);
+        const T d = matern_dist(s);
+        T e;
+        if constexpr (NU2 == 1) {
+            const T k = matern_poly_exp<NU2>(d, T(1), e);
+            if (phi) *phi = d == T(0) ? T(0) : -e / d;
+            return k;
+        } else if constexpr (NU2 == 3) {
+            const T k = matern_poly_exp<NU2>(d, t_fma(A, d, T(1)), e);
+            if (phi) *phi = T(-3) * e;
+            return k;
+        } else {
+            const T p1 = t_fma(A, d, T(1));
+            const T k = matern_poly_exp<NU2>(d, t_fma(T(5.0 / 3.0), s, p1), e);
+            if (phi) *phi = T(-5.0 / 3.0) * p1 * e;
+            return k;
+        }
+    }
+    __device__ __forceinline__ T eval(int64_t b, const P& r, const P& c) const { return os[b] * base(r, c); }
+    __device__ __forceinline__ P fcol(int64_t b, int64_t j) const { return col(b, j); }
+    __device__ __forceinline__ T feval(int64_t b, const P& r, const P& c) const { return eval(b, r, c); }
+    // row/col accumulators are in units of d/d(x/ls) ("scaled x"); pass 2 divides by ls.
+    __device__ __forceinline__ void grad(int64_t b, const P& r, const P& c, T g, T* ra, T* ca, T* ga) const {
+        T phi;
+        const T kb = base(r, c, &phi);
+        ga[DM] += g * kb;
+        const T w = g * phi * os[b];
+#pragma unroll
+        for (int d = 0; d < DM; ++d) {
+            const T df = r.x[d] - c.x[d];
+            ra[d] += w * df;
+            ca[d] -= w * df;
+            ga[d] -= w * df * df;             // * 1/ls applied in pass 2
+        }
+    }
+};
+
 // K2' batched  os * RBF-ARD(x; ls_r) * Periodic(x; ls_p, period):
 //   k = os * exp(-1/2 sum_d ((x_d - x'_d)/ls_r,d)^2) * exp(-2 sin^2(pi |x - x'| / period) / ls_p)
 // (gpytorch PeriodicKernel < 1.9 as recalled in SURVEY A.2/A.7: Euclidean distance of x / period, division by
@@ -675,6 +785,85 @@ int rbf_bwd(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, i
     }
 }
 
+template <typename T, int D, int NU2>
+int matern_fwd_d(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int Drt,
+                 int64_t sx1, int64_t sx2, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
+    MaternOp<T, D, NU2> op{x1, x2, ls, os, n1, n2, sx1, sx2, Drt};
+    return launch_fwd<T>(op, batch, n1, n2, diag_add, (const T*)nullptr, K, ldk, sK, stream);
+}
+
+template <typename T, int NU2>
+int matern_fwd_nu(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
+                  int64_t sx1, int64_t sx2, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
+    switch (D) {
+        case 1: return matern_fwd_d<T, 1, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
+        case 2: return matern_fwd_d<T, 2, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
+        case 3: return matern_fwd_d<T, 3, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
+        default: return matern_fwd_d<T, 0, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
+    }
+}
+
+template <typename T>
+int matern_fwd(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
+               int64_t sx1, int64_t sx2, int nu2, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
+    if (!x1) return -1; if (!x2) return -2; if (!ls) return -3; if (!os) return -4;
+    if (batch < 0) return -5; if (n1 < 0) return -6; if (n2 < 0) return -7; if (D < 1 || D > NSGP_MAX_DIM) return -8;
+    if (nu2 != 1 && nu2 != 3 && nu2 != 5) return -11;
+    if (!K && batch * n1 * n2 > 0) return -13; if (ldk < n2) return -14;
+    switch (nu2) {
+        case 1: return matern_fwd_nu<T, 1>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
+        case 3: return matern_fwd_nu<T, 3>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
+        default: return matern_fwd_nu<T, 5>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
+    }
+}
+
+template <typename T, int D, int NU2>
+int matern_bwd_d(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int Drt,
+                 int64_t sx1, int64_t sx2, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls, T* g_os,
+                 void* ws, size_t wsb, void* stream) {
+    using Op = MaternOp<T, D, NU2>;
+    Op op{x1, x2, ls, os, n1, n2, sx1, sx2, Drt};
+    constexpr int DM = Op::DM;
+    OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
+    for (int d = 0; d < Drt; ++d) {
+        if (g_x1) { rows.ptr[d] = g_x1 + d; rows.stride[d] = Drt; rows.bstride[d] = n1 * Drt;
+                    rows.div[d] = ls; rows.divstride[d] = Drt; rows.divoff[d] = d; }
+        if (g_x2) { cols.ptr[d] = g_x2 + d; cols.stride[d] = Drt; cols.bstride[d] = n2 * Drt;
+                    cols.div[d] = ls; cols.divstride[d] = Drt; cols.divoff[d] = d; }
+        if (g_ls) { globs.ptr[d] = g_ls + d; globs.bstride[d] = Drt;
+                    globs.div[d] = ls; globs.divstride[d] = Drt; globs.divoff[d] = d; }
+    }
+    if (g_os) { globs.ptr[DM] = g_os; globs.bstride[DM] = 1; }
+    return launch_bwd<T>(op, batch, n1, n2, G, ldg, sG, rows, cols, globs, ws, wsb, stream);
+}
+
+template <typename T, int NU2>
+int matern_bwd_nu(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
+                  int64_t sx1, int64_t sx2, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls, T* g_os,
+                  void* ws, size_t wsb, void* stream) {
+    switch (D) {
+        case 1: return matern_bwd_d<T, 1, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+        case 2: return matern_bwd_d<T, 2, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+        case 3: return matern_bwd_d<T, 3, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+        default: return matern_bwd_d<T, 0, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+    }
+}
+
+template <typename T>
+int matern_bwd(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
+               int64_t sx1, int64_t sx2, int nu2, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls,
+               T* g_os, void* ws, size_t wsb, void* stream) {
+    if (!x1) return -1; if (!x2) return -2; if (!ls) return -3; if (!os) return -4;
+    if (batch < 0) return -5; if (n1 < 0) return -6; if (n2 < 0) return -7; if (D < 1 || D > NSGP_MAX_DIM) return -8;
+    if (nu2 != 1 && nu2 != 3 && nu2 != 5) return -11;
+    if (!G && batch * n1 * n2 > 0) return -12; if (ldg < n2) return -13;
+    switch (nu2) {
+        case 1: return matern_bwd_nu<T, 1>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+        case 3: return matern_bwd_nu<T, 3>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+        default: return matern_bwd_nu<T, 5>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+    }
+}
+
 template <typename T>
 int ps_fwd(const T* x1, const T* x2, const T* s1, const T* s2, int64_t n1, int64_t n2, T jit, T* K, int64_t ldk,
            void* stream) {
@@ -806,6 +995,35 @@ int nsgp_rbf_build_bwd_f64(const double* x1, const double* x2, const double* ls,
                            int64_t sG, double* g_x1, double* g_x2, double* g_ls, double* g_os, void* ws,
                            size_t wsb, void* stream) {
     return rbf_bwd<double>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+}
+
+int nsgp_matern_build_fwd_f32(const float* x1, const float* x2, const float* ls, const float* os, int64_t batch,
+                              int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2, float diag_add, float* K,
+                              int64_t ldk, int64_t sK, void* stream) {
+    return matern_fwd<float>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, nu2, diag_add, K, ldk, sK, stream);
+}
+int nsgp_matern_build_fwd_f64(const double* x1, const double* x2, const double* ls, const double* os, int64_t batch,
+                              int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2, double diag_add,
+                              double* K, int64_t ldk, int64_t sK, void* stream) {
+    return matern_fwd<double>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, nu2, diag_add, K, ldk, sK, stream);
+}
+size_t nsgp_matern_build_bwd_workspace(int64_t batch, int64_t n1, int64_t n2, int D, int elem_size) {
+    (void)D;                                    // sized for the generic (NSGP_MAX_DIM) functor, any nu
+    return bwd_ws_elems<MaternOp<double, 0, 1>>(batch, n1, n2) * (size_t)elem_size + 256;
+}
+int nsgp_matern_build_bwd_f32(const float* x1, const float* x2, const float* ls, const float* os, int64_t batch,
+                              int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2, const float* G,
+                              int64_t ldg, int64_t sG, float* g_x1, float* g_x2, float* g_ls, float* g_os, void* ws,
+                              size_t wsb, void* stream) {
+    return matern_bwd<float>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, nu2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb,
+                             stream);
+}
+int nsgp_matern_build_bwd_f64(const double* x1, const double* x2, const double* ls, const double* os, int64_t batch,
+                              int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2, const double* G,
+                              int64_t ldg, int64_t sG, double* g_x1, double* g_x2, double* g_ls, double* g_os, void* ws,
+                              size_t wsb, void* stream) {
+    return matern_bwd<double>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, nu2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws,
+                              wsb, stream);
 }
 
 int nsgp_ps2d_build_fwd_f32(const float* x1, const float* x2, const float* s1, const float* s2, int64_t n1,

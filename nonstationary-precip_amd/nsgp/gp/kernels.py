@@ -1,9 +1,9 @@
 """Kernels [gpytorch.kernels semantics recalled, SURVEY A.2]: Kernel base (ard_num_dims, batch_shape,
 active_dims, softplus-constrained raw_lengthscale of shape (*batch, 1, D); unknown keyword arguments
 such as `lengthscale=` are swallowed exactly like gpytorch's Kernel.__init__(**kwargs) does),
-RBFKernel, ScaleKernel, InducingPointKernel, plus sum / product composition.
+RBFKernel, MaternKernel, ScaleKernel, InducingPointKernel, plus sum / product composition.
 
-Every matrix build runs on the gfx950 pairwise kernels (nsgp.ops.rbf_kernel / gibbs_kernel), with
+Every matrix build runs on the gfx950 pairwise kernels (nsgp.ops.rbf_kernel / matern_kernel / gibbs_kernel), with
 ScaleKernel's outputscale folded into the same launch."""
 import math
 
@@ -311,16 +311,48 @@ class PeriodicKernel(Kernel):
         return K.reshape(*bshape, K.shape[-2], K.shape[-1])
 
 
+def _matern(d, s, nu):
+    """k_nu(d) of MaternKernel (s = d^2), elementwise torch."""
+    if nu == 0.5:
+        return torch.exp(-d)
+    a = math.sqrt(2 * nu)
+    poly = 1 + a * d if nu == 1.5 else 1 + a * d + (5.0 / 3.0) * s
+    return poly * torch.exp(-a * d)
+
+
 class MaternKernel(Kernel):
-    """Declared for import compatibility (experiments/seard_spatial_benchmark.py:15); never exercised."""
+    """Matern-ARD, nu in {1/2, 3/2, 5/2}: k = e^-d, (1 + sqrt3 d) e^-sqrt3 d, (1 + sqrt5 d + 5/3 d^2) e^-sqrt5 d with
+    d = |(x1 - x2)/lengthscale| (models/latent_priors.py:106-123, experiments/seard_spatial_benchmark.py:15).  Built by
+    the gfx950 pairwise kernel (nsgp.ops.matern_kernel), ScaleKernel's outputscale folded into the same launch."""
     has_lengthscale = True
+    is_stationary = True
+    fuses_outputscale = True
 
     def __init__(self, nu=2.5, **kwargs):
+        if nu not in {0.5, 1.5, 2.5}:
+            raise RuntimeError('nu expected to be 0.5, 1.5, or 2.5')
         super().__init__(**kwargs)
         self.nu = nu
 
-    def forward(self, x1, x2, diag=False, **params):
-        raise NotImplementedError('MaternKernel is imported but not exercised by the reference hot path')
+    _flat = RBFKernel._flat
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, _outputscale=None, **params):
+        bshape, B, ls = self._flat(x1, x2)
+        if _outputscale is None:
+            os_ = torch.ones(B, dtype=x1.dtype, device=x1.device)
+        else:
+            os_ = _outputscale.expand(bshape).reshape(B) if _outputscale.dim() else _outputscale.expand(B)
+        if diag:
+            if same_points(x1, x2):
+                return os_.reshape(*bshape, 1).expand(*bshape, x1.shape[-2]) if len(bshape) else \
+                    os_.expand(x1.shape[-2])
+            s = ((x1 - x2) / self.lengthscale).pow(2).sum(-1)
+            k = _matern(s.clamp_min(1e-30).sqrt(), s, self.nu)       # d = 0: zero gradient, as the device kernel
+            return k * (os_.reshape(*bshape, 1) if len(bshape) else os_)
+        xa = x1.reshape(-1, *x1.shape[-2:]) if x1.dim() > 3 else x1
+        xb = x2.reshape(-1, *x2.shape[-2:]) if x2.dim() > 3 else x2
+        K = ops.matern_kernel(_batched_inputs(xa, B), _batched_inputs(xb, B), ls, os_.contiguous(), self.nu)
+        return K.reshape(*bshape, K.shape[-2], K.shape[-1])
 
 
 class InducingPointKernel(Kernel):

@@ -6,7 +6,7 @@ eager fallback: a CPU tensor or a missing library raises `BackendError`.
 
 Raw ops (no autograd) are lower-case functions returning new tensors; autograd entry points are the
 `*Fn` classes and the lower-case convenience wrappers at the bottom (`gibbs_kernel`, `rbf_kernel`,
-`ps2d_kernel`, `matmul`, `chol_inv`, ...).
+`matern_kernel`, `ps2d_kernel`, `matmul`, `chol_inv`, ...).
 """
 import ctypes
 import functools
@@ -217,24 +217,24 @@ def gibbs_build_bwd(x1, x2, ell1, ell2, outputscale, G, need_x=False, need_os=Tr
 # --------------------------------------------------------------------------------------------
 # K2 RBF-ARD (batched)
 # --------------------------------------------------------------------------------------------
-def _rbf_args(x1, x2, ls, os_):
+def _rbf_args(x1, x2, ls, os_, what='rbf_build'):
     ref = _chk(x1, x2, ls, os_)
     if ls.dim() == 1:
         ls = ls.unsqueeze(0)
     os_ = os_.reshape(-1)
     batch, D = ls.shape
     if os_.shape[0] != batch:
-        raise BackendError('rbf_build: os must be (batch,)')
+        raise BackendError(f'{what}: os must be (batch,)')
 
     def prep(x):
         if x.dim() == 2:
             if x.shape[1] != D:
-                raise BackendError('rbf_build: x last dim != D')
+                raise BackendError(f'{what}: x last dim != D')
             return _c(x), x.shape[0], 0
         if x.dim() == 3 and x.shape[0] == batch and x.shape[2] == D:
             x = _c(x)
             return x, x.shape[1], x.shape[1] * D
-        raise BackendError(f'rbf_build: x shape {tuple(x.shape)} vs batch {batch}, D {D}')
+        raise BackendError(f'{what}: x shape {tuple(x.shape)} vs batch {batch}, D {D}')
     x1, n1, sx1 = prep(x1)
     x2, n2, sx2 = prep(x2)
     return ref, x1, x2, _c(ls), _c(os_), batch, n1, n2, D, sx1, sx2
@@ -267,6 +267,50 @@ def rbf_build_bwd(x1, x2, ls, os_, G, need_x1=True, need_x2=True, sym=False):
     lib = _lib.load()
     ws = _ws(lib.nsgp_rbf_build_bwd_workspace(batch, n1, n2, D, ref.element_size()), ref.device)
     _lib.call(f'nsgp_rbf_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2,
+              _p(G), n2, n1 * n2, _p(g_x1), _p(g_x2), _p(g_ls), _p(g_os), _p(ws), ws.numel(), _stream())
+    return g_x1, g_x2, g_ls, g_os
+
+
+# --------------------------------------------------------------------------------------------
+# K2'' Matern-ARD (batched), nu in {1/2, 3/2, 5/2}
+# --------------------------------------------------------------------------------------------
+MATERN_NU = (0.5, 1.5, 2.5)
+
+
+def _nu2(nu):
+    if nu not in MATERN_NU:
+        raise BackendError(f'matern_build: nu must be one of {MATERN_NU}, got {nu}')
+    return int(2 * nu)
+
+
+def matern_build(x1, x2, ls, os_, nu, diag_add=0.0, out=None):
+    """K[b] = os[b] * Matern_nu(|(x1-x2)/ls[b]|) (+diag_add I).  Arguments and batching as rbf_build."""
+    nu2 = _nu2(nu)
+    ref, x1, x2, ls, os_, batch, n1, n2, D, sx1, sx2 = _rbf_args(x1, x2, ls, os_, 'matern_build')
+    K = _out_matrix(out, (batch, n1, n2), ref)
+    _lib.call(f'nsgp_matern_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2, nu2,
+              float(diag_add), _p(K), n2, n1 * n2, _stream())
+    return K
+
+
+def matern_build_bwd(x1, x2, ls, os_, nu, G, need_x1=True, need_x2=True, sym=False):
+    """As rbf_build_bwd: g_x1:(batch,n1,D) g_x2:(batch,n2,D) per batch, g_ls:(batch,D), g_os:(batch,); sym=True sums
+    both sides into one buffer.  For nu = 1/2 the derivative at zero distance is taken as 0."""
+    nu2 = _nu2(nu)
+    ref, x1, x2, ls, os_, batch, n1, n2, D, sx1, sx2 = _rbf_args(x1, x2, ls, os_, 'matern_build_bwd')
+    _chk(ref, G)
+    G = _c(G).reshape(batch, n1, n2)
+    g_x1 = torch.empty((batch, n1, D), dtype=ref.dtype, device=ref.device) if need_x1 else None
+    g_x2 = torch.empty((batch, n2, D), dtype=ref.dtype, device=ref.device) if need_x2 else None
+    if sym:
+        if n1 != n2 or sx1 != sx2 or not (need_x1 and need_x2):
+            raise BackendError('matern_build_bwd: sym needs x1 and x2 of one shape and both gradients')
+        g_x2 = g_x1
+    g_ls = torch.empty((batch, D), dtype=ref.dtype, device=ref.device)
+    g_os = torch.empty((batch,), dtype=ref.dtype, device=ref.device)
+    lib = _lib.load()
+    ws = _ws(lib.nsgp_matern_build_bwd_workspace(batch, n1, n2, D, ref.element_size()), ref.device)
+    _lib.call(f'nsgp_matern_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2, nu2,
               _p(G), n2, n1 * n2, _p(g_x1), _p(g_x2), _p(g_ls), _p(g_os), _p(ws), ws.numel(), _stream())
     return g_x1, g_x2, g_ls, g_os
 
@@ -1034,6 +1078,28 @@ class RbfKernelFn(torch.autograd.Function):
         return (g_x1 if n1g else None, g_x2 if n2g else None, g_ls.reshape(ls.shape), g_os.reshape(os_.shape), None)
 
 
+class MaternKernelFn(torch.autograd.Function):
+    """K[b] = os[b] Matern_nu-ARD(x1, x2; ls[b]) + diag_add I   (gpytorch ScaleKernel(MaternKernel(nu)))."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, ls, os_, nu, diag_add):
+        ctx.save_for_backward(x1, x2, ls, os_)
+        ctx.nu = nu
+        return matern_build(x1, x2, ls, os_, nu, diag_add)
+
+    @staticmethod
+    def backward(ctx, G):
+        x1, x2, ls, os_ = ctx.saved_tensors
+        n1g, n2g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g_x1, g_x2, g_ls, g_os = matern_build_bwd(x1, x2, ls, os_, ctx.nu, G, need_x1=n1g, need_x2=n2g)
+        if n1g and x1.dim() == 2:
+            g_x1 = g_x1.sum(0)
+        if n2g and x2.dim() == 2:
+            g_x2 = g_x2.sum(0)
+        return (g_x1 if n1g else None, g_x2 if n2g else None, g_ls.reshape(ls.shape), g_os.reshape(os_.shape), None,
+                None)
+
+
 class RbfPeriodicKernelFn(torch.autograd.Function):
     """K[b] = os[b] RBF-ARD(x; ls_rbf[b]) Periodic(x; ls_per[b], period[b]) + diag_add I; ls_rbf / os may be None
     (gpytorch ScaleKernel(RBFKernel * PeriodicKernel), models/spatio_temporal_models.py:22,42)."""
@@ -1161,6 +1227,11 @@ def gibbs_kernel(x1, x2, ell1, ell2, outputscale=None, diag_add=None):
 def rbf_kernel(x1, x2, ls, os_, diag_add=0.0):
     """Batched: returns (batch, n1, n2); ls:(batch,D) os:(batch,)."""
     return RbfKernelFn.apply(x1, x2, ls, os_, diag_add)
+
+
+def matern_kernel(x1, x2, ls, os_, nu, diag_add=0.0):
+    """Batched: returns (batch, n1, n2); ls:(batch,D) os:(batch,), nu in {0.5, 1.5, 2.5}."""
+    return MaternKernelFn.apply(x1, x2, ls, os_, nu, diag_add)
 
 
 def rbf_periodic_kernel(x1, x2, ls_rbf, ls_per, period, os_=None, diag_add=0.0):
