@@ -127,7 +127,7 @@ struct Epi {
     int p64;                // kind 1, MIX != 0: p0 / p1 are float64 buffers (the float64 accumulators' sums, unrounded)
     // MIX = 2: the B operand is never read -- B(k, n) = os[b] exp(-1/2 |z_k / ls[b] - x_n / ls[b]|^2) is generated in the
     // loader from the inducing points z (batch, K, D), the inputs x (n, D) or (batch, n, D) (kx_sx = batch stride),
-    // ls (batch, D), os (batch): the arithmetic of pairwise.hip's RbfOp, operation for operation
+    // ls (batch, D), os (batch): the arithmetic of pairwise.hip's ArdOp<T, D, RbfRadial>, operation for operation
     const float *kz, *kx, *kls, *kos;
     int kD;
     int64_t kx_sx;

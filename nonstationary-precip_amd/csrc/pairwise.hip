@@ -3,6 +3,13 @@
 //   K1 Gibbs (models/gibbs_kernels.py:154-162), K2 batched RBF-ARD (gpytorch ScaleKernel(RBF),
 //   models/dgps.py:44-46), K3 Paciorek-Schervish D=2 (models/multivariate_gibbs_kernel.py:98-150).
 //
+// Layout: a functor per kernel family (GibbsOp, ArdOp, RbfPeriodicOp, PsOp) is plugged into ONE forward tile kernel and
+// ONE backward tile kernel; dispatch_dim is the one place where the runtime D picks the specialised or generic functor.
+// The stationary ARD family os * kappa(|(x1 - x2) / ls|) is ONE functor, ArdOp<T, D, Radial>: RBF and Matern differ only
+// in the Radial policy.  To add a radial function: one policy struct (eval + negated, see RbfRadial), one extern "C"
+// forward/backward pair over ard_check / ard_fwd / ard_bwd, one ops.py wrapper pair over _ard_build / _ard_build_bwd, one
+// _StationaryArdKernel subclass in nsgp/gp/kernels.py.
+//
 // Forward: HBM-write bound.  One 256-thread workgroup owns a 64 x (64*CPT) tile; a lane owns CPT
 // consecutive columns (16 B) so every wave store is one contiguous 1 KiB line group; the column
 // operands live in registers for the whole tile and the row operands are computed once per tile and
@@ -20,6 +27,8 @@
 // registers and are combined across the 4 waves through LDS.  Tile partials go to a workspace and
 // a second tiny kernel sums them: deterministic, no atomics.
 #include "common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -104,61 +113,31 @@ template <typename T, int D> struct GibbsOp {
     }
 };
 
-template <typename T, int D> struct RbfOp {
-    static constexpr int DM = DimMax<D>::v;
-    static constexpr int NR = DM, NC = DM, NG = DM + 1;
-    const T *x1, *x2, *ls, *os;           // ls:(batch,D) os:(batch)
-    int64_t n1, n2, sx1, sx2;
-    int Drt;
-    struct P { T x[DM]; };                // pre-divided by the lengthscale
-    __device__ __forceinline__ P row(int64_t b, int64_t i) const {
-        P p;
-#pragma unroll
-        for (int d = 0; d < DM; ++d)
-            p.x[d] = (D || d < Drt) ? x1[b * sx1 + i * Drt + d] / ls[b * Drt + d] : T(0);
-        return p;
-    }
-    __device__ __forceinline__ P col(int64_t b, int64_t j) const {
-        P p;
-#pragma unroll
-        for (int d = 0; d < DM; ++d)
-            p.x[d] = (D || d < Drt) ? x2[b * sx2 + j * Drt + d] / ls[b * Drt + d] : T(0);
-        return p;
-    }
-    __device__ __forceinline__ T base(const P& r, const P& c) const {
-        T ex = T(0);
-#pragma unroll
-        for (int d = 0; d < DM; ++d) {
-            const T df = r.x[d] - c.x[d];
-            ex = t_fma(df, df, ex);                  // explicit: gemm.hip's generated-Kzx loader repeats this sum bit for bit
-        }
-        return t_fexp(T(-0.5) * ex);
-    }
-    __device__ __forceinline__ T eval(int64_t b, const P& r, const P& c) const { return os[b] * base(r, c); }
-    __device__ __forceinline__ P fcol(int64_t b, int64_t j) const { return col(b, j); }
-    __device__ __forceinline__ T feval(int64_t b, const P& r, const P& c) const { return eval(b, r, c); }
-    // row/col accumulators are in units of d/d(x/ls) ("scaled x"); pass 2 divides by ls.
-    __device__ __forceinline__ void grad(int64_t b, const P& r, const P& c, T g, T* ra, T* ca, T* ga) const {
-        const T kb = base(r, c);
-        ga[DM] += g * kb;
-        const T w = g * kb * os[b];
-#pragma unroll
-        for (int d = 0; d < DM; ++d) {
-            const T df = r.x[d] - c.x[d];
-            ra[d] -= w * df;
-            ca[d] += w * df;
-            ga[d] += w * df * df;             // * 1/ls applied in pass 2
-        }
+// K2 / K2'' batched stationary ARD kernels  k = os[b] * kappa(s),  s = |u|^2,  u = (x1 - x2) / ls[b]:  ONE functor, the
+// radial function kappa is the `Radial` policy (a template parameter only: no member, so the kernel-argument layout is
+// the same for every radial function).  A policy is stateless and has one function
+//     template <typename T> static T eval(T s, T* q = nullptr)
+// that returns kappa(s) and, when q != nullptr (the backward), also writes q = phi or q = -phi, where
+// phi = (d kappa / d d) / d <= 0 with d = sqrt(s), so that d kappa / d u_d = phi u_d.  `negated` says which: RBF writes
+// -phi (which IS kappa: nothing is computed twice), Matern writes phi.  ArdOp::grad accumulates with the matching signs.
+// Both spellings are the same mathematics, but not the same code: under -ffp-contract=fast the compiler picks which
+// multiply-add pairs to fuse from the spelling (with Matern in the -phi spelling the float32 nu = 1/2 backward stopped
+// fusing ga += g kappa and its g_os / g_x moved in the last bits), and RBF in the phi spelling costs the timed step up to
+// 14 instructions per kernel.  So each policy keeps the sign under which its results were established.
+struct RbfRadial {                        // kappa = exp(-s / 2), -phi = kappa
+    static constexpr bool negated = true;
+    template <typename T> static __device__ __forceinline__ T eval(T s, T* q = nullptr) {
+        const T k = t_fexp(T(-0.5) * s);
+        if (q) *q = k;
+        return k;
     }
 };
 
-// K2'' batched Matern-ARD, nu = NU2 / 2 in {1/2, 3/2, 5/2} (a template parameter: uniform per launch, so each entry
-// runs straight-line code with its constants folded; three instantiations per D and type).  Same operands, tiles and
-// batching as RbfOp.  u = (x1 - x2) / ls, s = sum_d u_d^2 (RbfOp's FMA chain), d = sqrt(s), a = sqrt(2 nu):
-//   nu = 1/2:  k = e^-d                          phi = (dk/dd) / d = -e^-d / d, 0 at d = 0
-//   nu = 3/2:  k = (1 + a d) e^-ad               phi = -3 e^-ad
-//   nu = 5/2:  k = (1 + a d + 5/3 s) e^-ad       phi = -5/3 (1 + a d) e^-ad
-// dk/du_d = phi u_d; the accumulators are RbfOp's with phi in place of -k (pass 2 divides by ls).
+// Matern, nu = NU2 / 2 in {1/2, 3/2, 5/2} (a template parameter: uniform per launch, so each entry runs straight-line
+// code with its constants folded; three instantiations per D and type).  d = sqrt(s), a = sqrt(2 nu):
+//   nu = 1/2:  kappa = e^-d                          phi = -e^-d / d, 0 at d = 0
+//   nu = 3/2:  kappa = (1 + a d) e^-ad               phi = -3 e^-ad
+//   nu = 5/2:  kappa = (1 + a d + 5/3 s) e^-ad       phi = -5/3 (1 + a d) e^-ad
 // d = 0 for nu = 1/2 is the symmetric subgradient (the limit of the other two): K(x, x)'s diagonal adds no gradient.
 // A NaN coordinate stays NaN (the d == 0 test is false for NaN); far entries are 0 * finite, never inf * 0.
 template <typename T> __device__ __forceinline__ T matern_dist(T s);
@@ -191,73 +170,76 @@ template <int NU2> __device__ __forceinline__ double matern_poly_exp(double d, d
     return poly * e;
 }
 
-template <typename T, int D, int NU2> struct MaternOp {
+template <int NU2> struct MaternRadial {
     static_assert(NU2 == 1 || NU2 == 3 || NU2 == 5, "nu = 1/2, 3/2, 5/2");
+    static constexpr bool negated = false;
+    template <typename T> static __device__ __forceinline__ T eval(T s, T* q = nullptr) {
+        constexpr T A = T(MaternA<NU2>::a);
+        const T d = matern_dist(s);
+        T e;
+        if constexpr (NU2 == 1) {
+            const T k = matern_poly_exp<NU2>(d, T(1), e);
+            if (q) *q = d == T(0) ? T(0) : -e / d;
+            return k;
+        } else if constexpr (NU2 == 3) {
+            const T k = matern_poly_exp<NU2>(d, t_fma(A, d, T(1)), e);
+            if (q) *q = T(-3) * e;
+            return k;
+        } else {
+            const T p1 = t_fma(A, d, T(1));
+            const T k = matern_poly_exp<NU2>(d, t_fma(T(5.0 / 3.0), s, p1), e);
+            if (q) *q = T(-5.0 / 3.0) * p1 * e;
+            return k;
+        }
+    }
+};
+
+template <typename T, int D, typename Radial> struct ArdOp {
     static constexpr int DM = DimMax<D>::v;
     static constexpr int NR = DM, NC = DM, NG = DM + 1;
-    static constexpr T A = T(MaternA<NU2>::a);
     const T *x1, *x2, *ls, *os;           // ls:(batch,D) os:(batch)
     int64_t n1, n2, sx1, sx2;
     int Drt;
     struct P { T x[DM]; };                // pre-divided by the lengthscale
-    __device__ __forceinline__ P row(int64_t b, int64_t i) const {
+    __device__ __forceinline__ P point(const T* x, int64_t sx, int64_t b, int64_t i) const {
         P p;
 #pragma unroll
         for (int d = 0; d < DM; ++d)
-            p.x[d] = (D || d < Drt) ? x1[b * sx1 + i * Drt + d] / ls[b * Drt + d] : T(0);
+            p.x[d] = (D || d < Drt) ? x[b * sx + i * Drt + d] / ls[b * Drt + d] : T(0);
         return p;
     }
-    __device__ __forceinline__ P col(int64_t b, int64_t j) const {
-        P p;
-#pragma unroll
-        for (int d = 0; d < DM; ++d)
-            p.x[d] = (D || d < Drt) ? x2[b * sx2 + j * Drt + d] / ls[b * Drt + d] : T(0);
-        return p;
-    }
+    __device__ __forceinline__ P row(int64_t b, int64_t i) const { return point(x1, sx1, b, i); }
+    __device__ __forceinline__ P col(int64_t b, int64_t j) const { return point(x2, sx2, b, j); }
     __device__ __forceinline__ T sq(const P& r, const P& c) const {
         T s = T(0);
 #pragma unroll
         for (int d = 0; d < DM; ++d) {
             const T df = r.x[d] - c.x[d];
-            s = t_fma(df, df, s);
+            s = t_fma(df, df, s);                    // explicit: gemm.hip's generated-Kzx loader repeats this sum bit for bit
         }
         return s;
     }
-    // k(d); with phi != nullptr also phi(d) = (dk/dd) / d
-    __device__ __forceinline__ T base(const P& r, const P& c, T* phi = nullptr) const {
-        const T s = sq(r, c);
-        const T d = matern_dist(s);
-        T e;
-        if constexpr (NU2 == 1) {
-            const T k = matern_poly_exp<NU2>(d, T(1), e);
-            if (phi) *phi = d == T(0) ? T(0) : -e / d;
-            return k;
-        } else if constexpr (NU2 == 3) {
-            const T k = matern_poly_exp<NU2>(d, t_fma(A, d, T(1)), e);
-            if (phi) *phi = T(-3) * e;
-            return k;
-        } else {
-            const T p1 = t_fma(A, d, T(1));
-            const T k = matern_poly_exp<NU2>(d, t_fma(T(5.0 / 3.0), s, p1), e);
-            if (phi) *phi = T(-5.0 / 3.0) * p1 * e;
-            return k;
-        }
-    }
-    __device__ __forceinline__ T eval(int64_t b, const P& r, const P& c) const { return os[b] * base(r, c); }
+    __device__ __forceinline__ T eval(int64_t b, const P& r, const P& c) const { return os[b] * Radial::eval(sq(r, c)); }
     __device__ __forceinline__ P fcol(int64_t b, int64_t j) const { return col(b, j); }
     __device__ __forceinline__ T feval(int64_t b, const P& r, const P& c) const { return eval(b, r, c); }
     // row/col accumulators are in units of d/d(x/ls) ("scaled x"); pass 2 divides by ls.
     __device__ __forceinline__ void grad(int64_t b, const P& r, const P& c, T g, T* ra, T* ca, T* ga) const {
-        T phi;
-        const T kb = base(r, c, &phi);
+        T q;
+        const T kb = Radial::eval(sq(r, c), &q);
         ga[DM] += g * kb;
-        const T w = g * phi * os[b];
+        const T w = g * q * os[b];
 #pragma unroll
         for (int d = 0; d < DM; ++d) {
             const T df = r.x[d] - c.x[d];
-            ra[d] += w * df;
-            ca[d] -= w * df;
-            ga[d] -= w * df * df;             // * 1/ls applied in pass 2
+            if constexpr (Radial::negated) {
+                ra[d] -= w * df;
+                ca[d] += w * df;
+                ga[d] += w * df * df;         // * 1/ls applied in pass 2
+            } else {
+                ra[d] += w * df;
+                ca[d] -= w * df;
+                ga[d] -= w * df * df;
+            }
         }
     }
 };
@@ -275,18 +257,14 @@ template <typename T, int D> struct RbfPeriodicOp {
     int64_t n1, n2, sx1, sx2;
     int Drt;
     struct P { T x[DM]; };
-    __device__ __forceinline__ P row(int64_t b, int64_t i) const {
+    __device__ __forceinline__ P point(const T* x, int64_t sx, int64_t b, int64_t i) const {
         P p;
 #pragma unroll
-        for (int d = 0; d < DM; ++d) p.x[d] = (D || d < Drt) ? x1[b * sx1 + i * Drt + d] : T(0);
+        for (int d = 0; d < DM; ++d) p.x[d] = (D || d < Drt) ? x[b * sx + i * Drt + d] : T(0);
         return p;
     }
-    __device__ __forceinline__ P col(int64_t b, int64_t j) const {
-        P p;
-#pragma unroll
-        for (int d = 0; d < DM; ++d) p.x[d] = (D || d < Drt) ? x2[b * sx2 + j * Drt + d] : T(0);
-        return p;
-    }
+    __device__ __forceinline__ P row(int64_t b, int64_t i) const { return point(x1, sx1, b, i); }
+    __device__ __forceinline__ P col(int64_t b, int64_t j) const { return point(x2, sx2, b, j); }
     // exponent pieces: q = sum_d (delta_d / ls_r,d)^2, r = |delta|, (s, c) = sincos(pi r / period)
     __device__ __forceinline__ T base(int64_t b, const P& r, const P& c, T& rr, T& sn, T& cs) const {
         T q = T(0), r2 = T(0);
@@ -676,11 +654,12 @@ template <typename T> OutDesc<T> empty_desc(int nval) {
 // ------------------------------------------------------------------------------------------
 // typed entry points
 // ------------------------------------------------------------------------------------------
-template <typename T, int D>
-int gibbs_fwd_d(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, int64_t n2, int Drt, const T* os,
-                const T* diag_add, T* K, int64_t ldk, void* stream) {
-    GibbsOp<T, D> op{x1, x2, l1, l2, n1, n2, Drt, os};
-    return launch_fwd<T>(op, 1, n1, n2, T(0), diag_add, K, ldk, 0, stream);
+// The one dispatch on the runtime dimension: f(std::integral_constant<int, D>{}) when D is one of the specialised
+// dimensions Ds, else f(std::integral_constant<int, 0>{}) (the generic functor: NSGP_MAX_DIM slots, runtime trip count).
+template <int... Ds, typename F> int dispatch_dim(int D, F&& f) {
+    int r = 0;
+    const bool hit = ((D == Ds && ((r = f(std::integral_constant<int, Ds>{})), true)) || ...);
+    return hit ? r : f(std::integral_constant<int, 0>{});
 }
 
 template <typename T>
@@ -689,30 +668,10 @@ int gibbs_fwd(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, in
     if (!x1) return -1; if (!x2) return -2; if (!l1) return -3; if (!l2) return -4;
     if (n1 < 0) return -5; if (n2 < 0) return -6; if (D < 1 || D > NSGP_MAX_DIM) return -7;
     if (!K && n1 * n2 > 0) return -10; if (ldk < n2) return -11;
-    switch (D) {
-        case 1: return gibbs_fwd_d<T, 1>(x1, x2, l1, l2, n1, n2, D, os, diag_add, K, ldk, stream);
-        case 2: return gibbs_fwd_d<T, 2>(x1, x2, l1, l2, n1, n2, D, os, diag_add, K, ldk, stream);
-        case 3: return gibbs_fwd_d<T, 3>(x1, x2, l1, l2, n1, n2, D, os, diag_add, K, ldk, stream);
-        default: return gibbs_fwd_d<T, 0>(x1, x2, l1, l2, n1, n2, D, os, diag_add, K, ldk, stream);
-    }
-}
-
-template <typename T, int D>
-int gibbs_bwd_d(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, int64_t n2, int Drt, const T* os,
-                const T* G, int64_t ldg, T* g_l1, T* g_l2, T* g_x1, T* g_x2, T* g_os, void* ws, size_t wsb,
-                void* stream) {
-    using Op = GibbsOp<T, D>;
-    Op op{x1, x2, l1, l2, n1, n2, Drt, os};
-    constexpr int DM = Op::DM;
-    OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
-    for (int d = 0; d < Drt; ++d) {
-        if (g_l1) { rows.ptr[d] = g_l1 + (int64_t)d * n1; rows.stride[d] = 1; }
-        if (g_x1) { rows.ptr[DM + d] = g_x1 + d; rows.stride[DM + d] = Drt; }
-        if (g_l2) { cols.ptr[d] = g_l2 + (int64_t)d * n2; cols.stride[d] = 1; }
-        if (g_x2) { cols.ptr[DM + d] = g_x2 + d; cols.stride[DM + d] = Drt; }
-    }
-    globs.ptr[0] = g_os;
-    return launch_bwd<T>(op, 1, n1, n2, G, ldg, 0, rows, cols, globs, ws, wsb, stream);
+    return dispatch_dim<1, 2, 3>(D, [&](auto d) {
+        GibbsOp<T, decltype(d)::value> op{x1, x2, l1, l2, n1, n2, D, os};
+        return launch_fwd<T>(op, 1, n1, n2, T(0), diag_add, K, ldk, 0, stream);
+    });
 }
 
 template <typename T>
@@ -721,147 +680,117 @@ int gibbs_bwd(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, in
     if (!x1) return -1; if (!x2) return -2; if (!l1) return -3; if (!l2) return -4;
     if (n1 < 0) return -5; if (n2 < 0) return -6; if (D < 1 || D > NSGP_MAX_DIM) return -7;
     if (!G && n1 * n2 > 0) return -9; if (ldg < n2) return -10;
-    switch (D) {
-        case 1: return gibbs_bwd_d<T, 1>(x1, x2, l1, l2, n1, n2, D, os, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb, stream);
-        case 2: return gibbs_bwd_d<T, 2>(x1, x2, l1, l2, n1, n2, D, os, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb, stream);
-        case 3: return gibbs_bwd_d<T, 3>(x1, x2, l1, l2, n1, n2, D, os, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb, stream);
-        default: return gibbs_bwd_d<T, 0>(x1, x2, l1, l2, n1, n2, D, os, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb, stream);
-    }
+    return dispatch_dim<1, 2, 3>(D, [&](auto dim) {
+        using Op = GibbsOp<T, decltype(dim)::value>;
+        Op op{x1, x2, l1, l2, n1, n2, D, os};
+        constexpr int DM = Op::DM;
+        OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
+        for (int d = 0; d < D; ++d) {
+            if (g_l1) { rows.ptr[d] = g_l1 + (int64_t)d * n1; rows.stride[d] = 1; }
+            if (g_x1) { rows.ptr[DM + d] = g_x1 + d; rows.stride[DM + d] = D; }
+            if (g_l2) { cols.ptr[d] = g_l2 + (int64_t)d * n2; cols.stride[d] = 1; }
+            if (g_x2) { cols.ptr[DM + d] = g_x2 + d; cols.stride[DM + d] = D; }
+        }
+        globs.ptr[0] = g_os;
+        return launch_bwd<T>(op, 1, n1, n2, G, ldg, 0, rows, cols, globs, ws, wsb, stream);
+    });
 }
 
-template <typename T, int D>
-int rbf_fwd_d(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int Drt,
-              int64_t sx1, int64_t sx2, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
-    RbfOp<T, D> op{x1, x2, ls, os, n1, n2, sx1, sx2, Drt};
-    return launch_fwd<T>(op, batch, n1, n2, diag_add, (const T*)nullptr, K, ldk, sK, stream);
+// Stationary ARD family (RBF, Matern): the inputs every entry point of the family takes, in signature order.
+template <typename T> struct ArdIn {
+    const T *x1, *x2, *ls, *os;
+    int64_t batch, n1, n2;
+    int D;
+    int64_t sx1, sx2;
+};
+
+// The family's argument check: 0, or the negative 1-based index of the first bad argument in the entry point's OWN
+// signature (C ABI).  The entry point's extra scalars (Matern: nu2) follow sx2 as arguments 11..10 + extra; `mat` is K
+// or G, which without extras is argument `mat_arg`, and `ld` its leading dimension, the argument after it.
+template <typename T>
+int ard_check(const ArdIn<T>& a, int extra, bool extra_ok, const T* mat, int64_t ld, int mat_arg) {
+    if (!a.x1) return -1; if (!a.x2) return -2; if (!a.ls) return -3; if (!a.os) return -4;
+    if (a.batch < 0) return -5; if (a.n1 < 0) return -6; if (a.n2 < 0) return -7;
+    if (a.D < 1 || a.D > NSGP_MAX_DIM) return -8;
+    if (!extra_ok) return -11;
+    if (!mat && a.batch * a.n1 * a.n2 > 0) return -(mat_arg + extra);
+    if (ld < a.n2) return -(mat_arg + extra + 1);
+    return 0;
+}
+constexpr int ARD_FWD_K = 12, ARD_BWD_G = 11;
+
+template <typename T, typename Radial>
+int ard_fwd(const ArdIn<T>& a, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
+    return dispatch_dim<1, 2, 3>(a.D, [&](auto d) {
+        ArdOp<T, decltype(d)::value, Radial> op{a.x1, a.x2, a.ls, a.os, a.n1, a.n2, a.sx1, a.sx2, a.D};
+        return launch_fwd<T>(op, a.batch, a.n1, a.n2, diag_add, (const T*)nullptr, K, ldk, sK, stream);
+    });
+}
+
+template <typename T, typename Radial>
+int ard_bwd(const ArdIn<T>& a, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls, T* g_os, void* ws,
+            size_t wsb, void* stream) {
+    return dispatch_dim<1, 2, 3>(a.D, [&](auto dim) {
+        using Op = ArdOp<T, decltype(dim)::value, Radial>;
+        Op op{a.x1, a.x2, a.ls, a.os, a.n1, a.n2, a.sx1, a.sx2, a.D};
+        constexpr int DM = Op::DM;
+        const int D = a.D;
+        OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
+        for (int d = 0; d < D; ++d) {
+            if (g_x1) { rows.ptr[d] = g_x1 + d; rows.stride[d] = D; rows.bstride[d] = a.n1 * D;
+                        rows.div[d] = a.ls; rows.divstride[d] = D; rows.divoff[d] = d; }
+            if (g_x2) { cols.ptr[d] = g_x2 + d; cols.stride[d] = D; cols.bstride[d] = a.n2 * D;
+                        cols.div[d] = a.ls; cols.divstride[d] = D; cols.divoff[d] = d; }
+            if (g_ls) { globs.ptr[d] = g_ls + d; globs.bstride[d] = D;
+                        globs.div[d] = a.ls; globs.divstride[d] = D; globs.divoff[d] = d; }
+        }
+        if (g_os) { globs.ptr[DM] = g_os; globs.bstride[DM] = 1; }
+        return launch_bwd<T>(op, a.batch, a.n1, a.n2, G, ldg, sG, rows, cols, globs, ws, wsb, stream);
+    });
 }
 
 template <typename T>
 int rbf_fwd(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
             int64_t sx1, int64_t sx2, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
-    if (!x1) return -1; if (!x2) return -2; if (!ls) return -3; if (!os) return -4;
-    if (batch < 0) return -5; if (n1 < 0) return -6; if (n2 < 0) return -7; if (D < 1 || D > NSGP_MAX_DIM) return -8;
-    if (!K && batch * n1 * n2 > 0) return -12; if (ldk < n2) return -13;
-    switch (D) {
-        case 1: return rbf_fwd_d<T, 1>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        case 2: return rbf_fwd_d<T, 2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        case 3: return rbf_fwd_d<T, 3>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        default: return rbf_fwd_d<T, 0>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-    }
-}
-
-template <typename T, int D>
-int rbf_bwd_d(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int Drt,
-              int64_t sx1, int64_t sx2, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls, T* g_os,
-              void* ws, size_t wsb, void* stream) {
-    using Op = RbfOp<T, D>;
-    Op op{x1, x2, ls, os, n1, n2, sx1, sx2, Drt};
-    constexpr int DM = Op::DM;
-    OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
-    for (int d = 0; d < Drt; ++d) {
-        if (g_x1) { rows.ptr[d] = g_x1 + d; rows.stride[d] = Drt; rows.bstride[d] = n1 * Drt;
-                    rows.div[d] = ls; rows.divstride[d] = Drt; rows.divoff[d] = d; }
-        if (g_x2) { cols.ptr[d] = g_x2 + d; cols.stride[d] = Drt; cols.bstride[d] = n2 * Drt;
-                    cols.div[d] = ls; cols.divstride[d] = Drt; cols.divoff[d] = d; }
-        if (g_ls) { globs.ptr[d] = g_ls + d; globs.bstride[d] = Drt;
-                    globs.div[d] = ls; globs.divstride[d] = Drt; globs.divoff[d] = d; }
-    }
-    if (g_os) { globs.ptr[DM] = g_os; globs.bstride[DM] = 1; }
-    return launch_bwd<T>(op, batch, n1, n2, G, ldg, sG, rows, cols, globs, ws, wsb, stream);
+    const ArdIn<T> a{x1, x2, ls, os, batch, n1, n2, D, sx1, sx2};
+    if (const int bad = ard_check(a, 0, true, (const T*)K, ldk, ARD_FWD_K)) return bad;
+    return ard_fwd<T, RbfRadial>(a, diag_add, K, ldk, sK, stream);
 }
 
 template <typename T>
 int rbf_bwd(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
             int64_t sx1, int64_t sx2, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls, T* g_os,
             void* ws, size_t wsb, void* stream) {
-    if (!x1) return -1; if (!x2) return -2; if (!ls) return -3; if (!os) return -4;
-    if (batch < 0) return -5; if (n1 < 0) return -6; if (n2 < 0) return -7; if (D < 1 || D > NSGP_MAX_DIM) return -8;
-    if (!G && batch * n1 * n2 > 0) return -11; if (ldg < n2) return -12;
-    switch (D) {
-        case 1: return rbf_bwd_d<T, 1>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-        case 2: return rbf_bwd_d<T, 2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-        case 3: return rbf_bwd_d<T, 3>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-        default: return rbf_bwd_d<T, 0>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-    }
+    const ArdIn<T> a{x1, x2, ls, os, batch, n1, n2, D, sx1, sx2};
+    if (const int bad = ard_check(a, 0, true, G, ldg, ARD_BWD_G)) return bad;
+    return ard_bwd<T, RbfRadial>(a, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
 }
 
-template <typename T, int D, int NU2>
-int matern_fwd_d(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int Drt,
-                 int64_t sx1, int64_t sx2, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
-    MaternOp<T, D, NU2> op{x1, x2, ls, os, n1, n2, sx1, sx2, Drt};
-    return launch_fwd<T>(op, batch, n1, n2, diag_add, (const T*)nullptr, K, ldk, sK, stream);
-}
-
-template <typename T, int NU2>
-int matern_fwd_nu(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
-                  int64_t sx1, int64_t sx2, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
-    switch (D) {
-        case 1: return matern_fwd_d<T, 1, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        case 2: return matern_fwd_d<T, 2, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        case 3: return matern_fwd_d<T, 3, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        default: return matern_fwd_d<T, 0, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-    }
+// nu2 = 2 nu (checked by the caller) -> f(MaternRadial<nu2>{})
+static inline bool matern_nu2_ok(int nu2) { return nu2 == 1 || nu2 == 3 || nu2 == 5; }
+template <typename F> int dispatch_nu2(int nu2, F&& f) {
+    return nu2 == 1 ? f(MaternRadial<1>{}) : nu2 == 3 ? f(MaternRadial<3>{}) : f(MaternRadial<5>{});
 }
 
 template <typename T>
 int matern_fwd(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
                int64_t sx1, int64_t sx2, int nu2, T diag_add, T* K, int64_t ldk, int64_t sK, void* stream) {
-    if (!x1) return -1; if (!x2) return -2; if (!ls) return -3; if (!os) return -4;
-    if (batch < 0) return -5; if (n1 < 0) return -6; if (n2 < 0) return -7; if (D < 1 || D > NSGP_MAX_DIM) return -8;
-    if (nu2 != 1 && nu2 != 3 && nu2 != 5) return -11;
-    if (!K && batch * n1 * n2 > 0) return -13; if (ldk < n2) return -14;
-    switch (nu2) {
-        case 1: return matern_fwd_nu<T, 1>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        case 3: return matern_fwd_nu<T, 3>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        default: return matern_fwd_nu<T, 5>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-    }
-}
-
-template <typename T, int D, int NU2>
-int matern_bwd_d(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int Drt,
-                 int64_t sx1, int64_t sx2, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls, T* g_os,
-                 void* ws, size_t wsb, void* stream) {
-    using Op = MaternOp<T, D, NU2>;
-    Op op{x1, x2, ls, os, n1, n2, sx1, sx2, Drt};
-    constexpr int DM = Op::DM;
-    OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
-    for (int d = 0; d < Drt; ++d) {
-        if (g_x1) { rows.ptr[d] = g_x1 + d; rows.stride[d] = Drt; rows.bstride[d] = n1 * Drt;
-                    rows.div[d] = ls; rows.divstride[d] = Drt; rows.divoff[d] = d; }
-        if (g_x2) { cols.ptr[d] = g_x2 + d; cols.stride[d] = Drt; cols.bstride[d] = n2 * Drt;
-                    cols.div[d] = ls; cols.divstride[d] = Drt; cols.divoff[d] = d; }
-        if (g_ls) { globs.ptr[d] = g_ls + d; globs.bstride[d] = Drt;
-                    globs.div[d] = ls; globs.divstride[d] = Drt; globs.divoff[d] = d; }
-    }
-    if (g_os) { globs.ptr[DM] = g_os; globs.bstride[DM] = 1; }
-    return launch_bwd<T>(op, batch, n1, n2, G, ldg, sG, rows, cols, globs, ws, wsb, stream);
-}
-
-template <typename T, int NU2>
-int matern_bwd_nu(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
-                  int64_t sx1, int64_t sx2, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls, T* g_os,
-                  void* ws, size_t wsb, void* stream) {
-    switch (D) {
-        case 1: return matern_bwd_d<T, 1, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-        case 2: return matern_bwd_d<T, 2, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-        case 3: return matern_bwd_d<T, 3, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-        default: return matern_bwd_d<T, 0, NU2>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-    }
+    const ArdIn<T> a{x1, x2, ls, os, batch, n1, n2, D, sx1, sx2};
+    if (const int bad = ard_check(a, 1, matern_nu2_ok(nu2), (const T*)K, ldk, ARD_FWD_K)) return bad;
+    return dispatch_nu2(nu2, [&](auto radial) {
+        return ard_fwd<T, decltype(radial)>(a, diag_add, K, ldk, sK, stream);
+    });
 }
 
 template <typename T>
 int matern_bwd(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch, int64_t n1, int64_t n2, int D,
                int64_t sx1, int64_t sx2, int nu2, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_ls,
                T* g_os, void* ws, size_t wsb, void* stream) {
-    if (!x1) return -1; if (!x2) return -2; if (!ls) return -3; if (!os) return -4;
-    if (batch < 0) return -5; if (n1 < 0) return -6; if (n2 < 0) return -7; if (D < 1 || D > NSGP_MAX_DIM) return -8;
-    if (nu2 != 1 && nu2 != 3 && nu2 != 5) return -11;
-    if (!G && batch * n1 * n2 > 0) return -12; if (ldg < n2) return -13;
-    switch (nu2) {
-        case 1: return matern_bwd_nu<T, 1>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-        case 3: return matern_bwd_nu<T, 3>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-        default: return matern_bwd_nu<T, 5>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
-    }
+    const ArdIn<T> a{x1, x2, ls, os, batch, n1, n2, D, sx1, sx2};
+    if (const int bad = ard_check(a, 1, matern_nu2_ok(nu2), G, ldg, ARD_BWD_G)) return bad;
+    return dispatch_nu2(nu2, [&](auto radial) {
+        return ard_bwd<T, decltype(radial)>(a, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+    });
 }
 
 template <typename T>
@@ -888,13 +817,6 @@ int ps_bwd(const T* x1, const T* x2, const T* s1, const T* s2, int64_t n1, int64
     return launch_bwd<T>(op, 1, n1, n2, G, ldg, 0, rows, cols, globs, ws, wsb, stream);
 }
 
-template <typename T, int D>
-int rbfper_fwd_d(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* per, const T* os, int64_t batch,
-                 int64_t n1, int64_t n2, int Drt, int64_t sx1, int64_t sx2, T diag_add, T* K, int64_t ldk, int64_t sK,
-                 void* stream) {
-    RbfPeriodicOp<T, D> op{x1, x2, lsr, lsp, per, os, n1, n2, sx1, sx2, Drt};
-    return launch_fwd<T>(op, batch, n1, n2, diag_add, (const T*)nullptr, K, ldk, sK, stream);
-}
 template <typename T>
 int rbfper_fwd(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* per, const T* os, int64_t batch,
                int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, T diag_add, T* K, int64_t ldk, int64_t sK,
@@ -902,29 +824,10 @@ int rbfper_fwd(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* pe
     if (!x1) return -1; if (!x2) return -2; if (!lsp) return -4; if (!per) return -5;
     if (batch < 0) return -7; if (n1 < 0) return -8; if (n2 < 0) return -9; if (D < 1 || D > NSGP_MAX_DIM) return -10;
     if (!K && batch * n1 * n2 > 0) return -14; if (ldk < n2) return -15;
-    switch (D) {
-        case 1: return rbfper_fwd_d<T, 1>(x1, x2, lsr, lsp, per, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        case 2: return rbfper_fwd_d<T, 2>(x1, x2, lsr, lsp, per, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-        default: return rbfper_fwd_d<T, 0>(x1, x2, lsr, lsp, per, os, batch, n1, n2, D, sx1, sx2, diag_add, K, ldk, sK, stream);
-    }
-}
-template <typename T, int D>
-int rbfper_bwd_d(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* per, const T* os, int64_t batch,
-                 int64_t n1, int64_t n2, int Drt, int64_t sx1, int64_t sx2, const T* G, int64_t ldg, int64_t sG,
-                 T* g_x1, T* g_x2, T* g_lsr, T* g_lsp, T* g_per, T* g_os, void* ws, size_t wsb, void* stream) {
-    using Op = RbfPeriodicOp<T, D>;
-    Op op{x1, x2, lsr, lsp, per, os, n1, n2, sx1, sx2, Drt};
-    constexpr int DM = Op::DM;
-    OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
-    for (int d = 0; d < Drt; ++d) {
-        if (g_x1) { rows.ptr[d] = g_x1 + d; rows.stride[d] = Drt; rows.bstride[d] = n1 * Drt; }
-        if (g_x2) { cols.ptr[d] = g_x2 + d; cols.stride[d] = Drt; cols.bstride[d] = n2 * Drt; }
-        if (g_lsr && lsr) { globs.ptr[d] = g_lsr + d; globs.bstride[d] = Drt; }
-    }
-    if (g_lsp) { globs.ptr[DM] = g_lsp; globs.bstride[DM] = 1; }
-    if (g_per) { globs.ptr[DM + 1] = g_per; globs.bstride[DM + 1] = 1; }
-    if (g_os) { globs.ptr[DM + 2] = g_os; globs.bstride[DM + 2] = 1; }
-    return launch_bwd<T>(op, batch, n1, n2, G, ldg, sG, rows, cols, globs, ws, wsb, stream);
+    return dispatch_dim<1, 2>(D, [&](auto d) {
+        RbfPeriodicOp<T, decltype(d)::value> op{x1, x2, lsr, lsp, per, os, n1, n2, sx1, sx2, D};
+        return launch_fwd<T>(op, batch, n1, n2, diag_add, (const T*)nullptr, K, ldk, sK, stream);
+    });
 }
 template <typename T>
 int rbfper_bwd(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* per, const T* os, int64_t batch,
@@ -933,11 +836,21 @@ int rbfper_bwd(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* pe
     if (!x1) return -1; if (!x2) return -2; if (!lsp) return -4; if (!per) return -5;
     if (batch < 0) return -7; if (n1 < 0) return -8; if (n2 < 0) return -9; if (D < 1 || D > NSGP_MAX_DIM) return -10;
     if (!G && batch * n1 * n2 > 0) return -13; if (ldg < n2) return -14;
-    switch (D) {
-        case 1: return rbfper_bwd_d<T, 1>(x1, x2, lsr, lsp, per, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_lsr, g_lsp, g_per, g_os, ws, wsb, stream);
-        case 2: return rbfper_bwd_d<T, 2>(x1, x2, lsr, lsp, per, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_lsr, g_lsp, g_per, g_os, ws, wsb, stream);
-        default: return rbfper_bwd_d<T, 0>(x1, x2, lsr, lsp, per, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2, g_lsr, g_lsp, g_per, g_os, ws, wsb, stream);
-    }
+    return dispatch_dim<1, 2>(D, [&](auto dim) {
+        using Op = RbfPeriodicOp<T, decltype(dim)::value>;
+        Op op{x1, x2, lsr, lsp, per, os, n1, n2, sx1, sx2, D};
+        constexpr int DM = Op::DM;
+        OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
+        for (int d = 0; d < D; ++d) {
+            if (g_x1) { rows.ptr[d] = g_x1 + d; rows.stride[d] = D; rows.bstride[d] = n1 * D; }
+            if (g_x2) { cols.ptr[d] = g_x2 + d; cols.stride[d] = D; cols.bstride[d] = n2 * D; }
+            if (g_lsr && lsr) { globs.ptr[d] = g_lsr + d; globs.bstride[d] = D; }
+        }
+        if (g_lsp) { globs.ptr[DM] = g_lsp; globs.bstride[DM] = 1; }
+        if (g_per) { globs.ptr[DM + 1] = g_per; globs.bstride[DM + 1] = 1; }
+        if (g_os) { globs.ptr[DM + 2] = g_os; globs.bstride[DM + 2] = 1; }
+        return launch_bwd<T>(op, batch, n1, n2, G, ldg, sG, rows, cols, globs, ws, wsb, stream);
+    });
 }
 
 }  // namespace
@@ -982,7 +895,7 @@ int nsgp_rbf_build_fwd_f64(const double* x1, const double* x2, const double* ls,
 }
 size_t nsgp_rbf_build_bwd_workspace(int64_t batch, int64_t n1, int64_t n2, int D, int elem_size) {
     (void)D;
-    return bwd_ws_elems<RbfOp<double, 0>>(batch, n1, n2) * (size_t)elem_size + 256;
+    return bwd_ws_elems<ArdOp<double, 0, RbfRadial>>(batch, n1, n2) * (size_t)elem_size + 256;
 }
 int nsgp_rbf_build_bwd_f32(const float* x1, const float* x2, const float* ls, const float* os, int64_t batch,
                            int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, const float* G, int64_t ldg,
@@ -1008,8 +921,8 @@ int nsgp_matern_build_fwd_f64(const double* x1, const double* x2, const double* 
     return matern_fwd<double>(x1, x2, ls, os, batch, n1, n2, D, sx1, sx2, nu2, diag_add, K, ldk, sK, stream);
 }
 size_t nsgp_matern_build_bwd_workspace(int64_t batch, int64_t n1, int64_t n2, int D, int elem_size) {
-    (void)D;                                    // sized for the generic (NSGP_MAX_DIM) functor, any nu
-    return bwd_ws_elems<MaternOp<double, 0, 1>>(batch, n1, n2) * (size_t)elem_size + 256;
+    (void)D;                                    // sized for the generic (NSGP_MAX_DIM) functor, any radial function
+    return bwd_ws_elems<ArdOp<double, 0, RbfRadial>>(batch, n1, n2) * (size_t)elem_size + 256;
 }
 int nsgp_matern_build_bwd_f32(const float* x1, const float* x2, const float* ls, const float* os, int64_t batch,
                               int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2, const float* G,

@@ -121,10 +121,18 @@ def _batched_inputs(x, B):
     raise ops.BackendError(f'kernel inputs of shape {tuple(x.shape)} do not match kernel batch {B}')
 
 
-class RBFKernel(Kernel):
-    """exp(-1/2 |(x1 - x2)/lengthscale|^2)  (models/dgps.py:44-46, models/gibbs_kernels.py:67-69)."""
+class _StationaryArdKernel(Kernel):
+    """outputscale * kappa(|(x1 - x2)/lengthscale|^2): one forward for the family.  A subclass gives kappa twice: as
+    elementwise torch on the squared distance (`_radial`, the diag=True path) and as its pairwise build on the device
+    (`_build`, one launch with the outputscale folded in)."""
     has_lengthscale = True
     is_stationary = True
+
+    def _radial(self, s):
+        raise NotImplementedError
+
+    def _build(self, x1, x2, ls, os_):
+        raise NotImplementedError
 
     def _flat(self, x1, x2):
         ls = self.lengthscale                                  # (*batch, 1, D)
@@ -146,12 +154,22 @@ class RBFKernel(Kernel):
             if same_points(x1, x2):
                 return os_.reshape(*bshape, 1).expand(*bshape, x1.shape[-2]) if len(bshape) else \
                     os_.expand(x1.shape[-2])
-            d = ((x1 - x2) / self.lengthscale).pow(2).sum(-1)
-            return torch.exp(-0.5 * d) * (os_.reshape(*bshape, 1) if len(bshape) else os_)
+            s = ((x1 - x2) / self.lengthscale).pow(2).sum(-1)
+            return self._radial(s) * (os_.reshape(*bshape, 1) if len(bshape) else os_)
         xa = x1.reshape(-1, *x1.shape[-2:]) if x1.dim() > 3 else x1
         xb = x2.reshape(-1, *x2.shape[-2:]) if x2.dim() > 3 else x2
-        K = ops.rbf_kernel(_batched_inputs(xa, B), _batched_inputs(xb, B), ls, os_.contiguous())
+        K = self._build(_batched_inputs(xa, B), _batched_inputs(xb, B), ls, os_.contiguous())
         return K.reshape(*bshape, K.shape[-2], K.shape[-1])
+
+
+class RBFKernel(_StationaryArdKernel):
+    """exp(-1/2 |(x1 - x2)/lengthscale|^2)  (models/dgps.py:44-46, models/gibbs_kernels.py:67-69)."""
+
+    def _radial(self, s):
+        return torch.exp(-0.5 * s)
+
+    def _build(self, x1, x2, ls, os_):
+        return ops.rbf_kernel(x1, x2, ls, os_)
 
 
 class ScaleKernel(Kernel):
@@ -320,12 +338,10 @@ def _matern(d, s, nu):
     return poly * torch.exp(-a * d)
 
 
-class MaternKernel(Kernel):
+class MaternKernel(_StationaryArdKernel):
     """Matern-ARD, nu in {1/2, 3/2, 5/2}: k = e^-d, (1 + sqrt3 d) e^-sqrt3 d, (1 + sqrt5 d + 5/3 d^2) e^-sqrt5 d with
     d = |(x1 - x2)/lengthscale| (models/latent_priors.py:106-123, experiments/seard_spatial_benchmark.py:15).  Built by
     the gfx950 pairwise kernel (nsgp.ops.matern_kernel), ScaleKernel's outputscale folded into the same launch."""
-    has_lengthscale = True
-    is_stationary = True
     fuses_outputscale = True
 
     def __init__(self, nu=2.5, **kwargs):
@@ -334,25 +350,11 @@ class MaternKernel(Kernel):
         super().__init__(**kwargs)
         self.nu = nu
 
-    _flat = RBFKernel._flat
+    def _radial(self, s):
+        return _matern(s.clamp_min(1e-30).sqrt(), s, self.nu)        # d = 0: zero gradient, as the device kernel
 
-    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, _outputscale=None, **params):
-        bshape, B, ls = self._flat(x1, x2)
-        if _outputscale is None:
-            os_ = torch.ones(B, dtype=x1.dtype, device=x1.device)
-        else:
-            os_ = _outputscale.expand(bshape).reshape(B) if _outputscale.dim() else _outputscale.expand(B)
-        if diag:
-            if same_points(x1, x2):
-                return os_.reshape(*bshape, 1).expand(*bshape, x1.shape[-2]) if len(bshape) else \
-                    os_.expand(x1.shape[-2])
-            s = ((x1 - x2) / self.lengthscale).pow(2).sum(-1)
-            k = _matern(s.clamp_min(1e-30).sqrt(), s, self.nu)       # d = 0: zero gradient, as the device kernel
-            return k * (os_.reshape(*bshape, 1) if len(bshape) else os_)
-        xa = x1.reshape(-1, *x1.shape[-2:]) if x1.dim() > 3 else x1
-        xb = x2.reshape(-1, *x2.shape[-2:]) if x2.dim() > 3 else x2
-        K = ops.matern_kernel(_batched_inputs(xa, B), _batched_inputs(xb, B), ls, os_.contiguous(), self.nu)
-        return K.reshape(*bshape, K.shape[-2], K.shape[-1])
+    def _build(self, x1, x2, ls, os_):
+        return ops.matern_kernel(x1, x2, ls, os_, self.nu)
 
 
 class InducingPointKernel(Kernel):

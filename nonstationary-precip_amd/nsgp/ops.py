@@ -217,7 +217,19 @@ def gibbs_build_bwd(x1, x2, ell1, ell2, outputscale, G, need_x=False, need_os=Tr
 # --------------------------------------------------------------------------------------------
 # K2 RBF-ARD (batched)
 # --------------------------------------------------------------------------------------------
-def _rbf_args(x1, x2, ls, os_, what='rbf_build'):
+def _shared_or_batched(x, batch, D, what):
+    """x:(n,D) shared by the batch or (batch,n,D) -> (contiguous x, n, its batch stride in elements: 0 when shared)."""
+    if x.dim() == 2:
+        if x.shape[1] != D:
+            raise BackendError(f'{what}: x last dim != D')
+        return _c(x), x.shape[0], 0
+    if x.dim() == 3 and x.shape[0] == batch and x.shape[2] == D:
+        x = _c(x)
+        return x, x.shape[1], x.shape[1] * D
+    raise BackendError(f'{what}: x shape {tuple(x.shape)} vs batch {batch}, D {D}')
+
+
+def _rbf_args(x1, x2, ls, os_, what):
     ref = _chk(x1, x2, ls, os_)
     if ls.dim() == 1:
         ls = ls.unsqueeze(0)
@@ -225,50 +237,52 @@ def _rbf_args(x1, x2, ls, os_, what='rbf_build'):
     batch, D = ls.shape
     if os_.shape[0] != batch:
         raise BackendError(f'{what}: os must be (batch,)')
-
-    def prep(x):
-        if x.dim() == 2:
-            if x.shape[1] != D:
-                raise BackendError(f'{what}: x last dim != D')
-            return _c(x), x.shape[0], 0
-        if x.dim() == 3 and x.shape[0] == batch and x.shape[2] == D:
-            x = _c(x)
-            return x, x.shape[1], x.shape[1] * D
-        raise BackendError(f'{what}: x shape {tuple(x.shape)} vs batch {batch}, D {D}')
-    x1, n1, sx1 = prep(x1)
-    x2, n2, sx2 = prep(x2)
+    x1, n1, sx1 = _shared_or_batched(x1, batch, D, what)
+    x2, n2, sx2 = _shared_or_batched(x2, batch, D, what)
     return ref, x1, x2, _c(ls), _c(os_), batch, n1, n2, D, sx1, sx2
 
 
-def rbf_build(x1, x2, ls, os_, diag_add=0.0, out=None):
-    """K[b] = os[b] * exp(-0.5 |(x1-x2)/ls[b]|^2) (+diag_add I).  x:(n,D) shared or (batch,n,D)."""
-    ref, x1, x2, ls, os_, batch, n1, n2, D, sx1, sx2 = _rbf_args(x1, x2, ls, os_)
+# The stationary ARD family K[b] = os[b] * kappa(|(x1-x2)/ls[b]|) shares its argument rules, allocation and call shape;
+# a member is its library stem (nsgp_<stem>_build_fwd/_bwd_*) plus the extra scalar arguments its entry points take
+# after sx2 (Matern: nu2).
+def _ard_build(stem, extra, x1, x2, ls, os_, diag_add, out):
+    ref, x1, x2, ls, os_, batch, n1, n2, D, sx1, sx2 = _rbf_args(x1, x2, ls, os_, f'{stem}_build')
     K = _out_matrix(out, (batch, n1, n2), ref)
-    _lib.call(f'nsgp_rbf_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2,
+    _lib.call(f'nsgp_{stem}_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2, *extra,
               float(diag_add), _p(K), n2, n1 * n2, _stream())
     return K
 
 
-def rbf_build_bwd(x1, x2, ls, os_, G, need_x1=True, need_x2=True, sym=False):
-    """Returns g_x1:(batch,n1,D) g_x2:(batch,n2,D) (per-batch, caller sums if x was shared) g_ls, g_os.
-    sym=True (x1 is x2, the Kzz case): ONE buffer receives the sum of the row- and column-side gradients and is
-    returned for both."""
-    ref, x1, x2, ls, os_, batch, n1, n2, D, sx1, sx2 = _rbf_args(x1, x2, ls, os_)
+def _ard_build_bwd(stem, extra, x1, x2, ls, os_, G, need_x1, need_x2, sym):
+    what = f'{stem}_build_bwd'
+    ref, x1, x2, ls, os_, batch, n1, n2, D, sx1, sx2 = _rbf_args(x1, x2, ls, os_, what)
     _chk(ref, G)
     G = _c(G).reshape(batch, n1, n2)
     g_x1 = torch.empty((batch, n1, D), dtype=ref.dtype, device=ref.device) if need_x1 else None
     g_x2 = torch.empty((batch, n2, D), dtype=ref.dtype, device=ref.device) if need_x2 else None
     if sym:
         if n1 != n2 or sx1 != sx2 or not (need_x1 and need_x2):
-            raise BackendError('rbf_build_bwd: sym needs x1 and x2 of one shape and both gradients')
+            raise BackendError(f'{what}: sym needs x1 and x2 of one shape and both gradients')
         g_x2 = g_x1
     g_ls = torch.empty((batch, D), dtype=ref.dtype, device=ref.device)
     g_os = torch.empty((batch,), dtype=ref.dtype, device=ref.device)
-    lib = _lib.load()
-    ws = _ws(lib.nsgp_rbf_build_bwd_workspace(batch, n1, n2, D, ref.element_size()), ref.device)
-    _lib.call(f'nsgp_rbf_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2,
+    workspace = getattr(_lib.load(), f'nsgp_{stem}_build_bwd_workspace')
+    ws = _ws(workspace(batch, n1, n2, D, ref.element_size()), ref.device)
+    _lib.call(f'nsgp_{stem}_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2, *extra,
               _p(G), n2, n1 * n2, _p(g_x1), _p(g_x2), _p(g_ls), _p(g_os), _p(ws), ws.numel(), _stream())
     return g_x1, g_x2, g_ls, g_os
+
+
+def rbf_build(x1, x2, ls, os_, diag_add=0.0, out=None):
+    """K[b] = os[b] * exp(-0.5 |(x1-x2)/ls[b]|^2) (+diag_add I).  x:(n,D) shared or (batch,n,D)."""
+    return _ard_build('rbf', (), x1, x2, ls, os_, diag_add, out)
+
+
+def rbf_build_bwd(x1, x2, ls, os_, G, need_x1=True, need_x2=True, sym=False):
+    """Returns g_x1:(batch,n1,D) g_x2:(batch,n2,D) (per-batch, caller sums if x was shared) g_ls, g_os.
+    sym=True (x1 is x2, the Kzz case): ONE buffer receives the sum of the row- and column-side gradients and is
+    returned for both."""
+    return _ard_build_bwd('rbf', (), x1, x2, ls, os_, G, need_x1, need_x2, sym)
 
 
 # --------------------------------------------------------------------------------------------
@@ -285,34 +299,13 @@ def _nu2(nu):
 
 def matern_build(x1, x2, ls, os_, nu, diag_add=0.0, out=None):
     """K[b] = os[b] * Matern_nu(|(x1-x2)/ls[b]|) (+diag_add I).  Arguments and batching as rbf_build."""
-    nu2 = _nu2(nu)
-    ref, x1, x2, ls, os_, batch, n1, n2, D, sx1, sx2 = _rbf_args(x1, x2, ls, os_, 'matern_build')
-    K = _out_matrix(out, (batch, n1, n2), ref)
-    _lib.call(f'nsgp_matern_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2, nu2,
-              float(diag_add), _p(K), n2, n1 * n2, _stream())
-    return K
+    return _ard_build('matern', (_nu2(nu),), x1, x2, ls, os_, diag_add, out)
 
 
 def matern_build_bwd(x1, x2, ls, os_, nu, G, need_x1=True, need_x2=True, sym=False):
     """As rbf_build_bwd: g_x1:(batch,n1,D) g_x2:(batch,n2,D) per batch, g_ls:(batch,D), g_os:(batch,); sym=True sums
     both sides into one buffer.  For nu = 1/2 the derivative at zero distance is taken as 0."""
-    nu2 = _nu2(nu)
-    ref, x1, x2, ls, os_, batch, n1, n2, D, sx1, sx2 = _rbf_args(x1, x2, ls, os_, 'matern_build_bwd')
-    _chk(ref, G)
-    G = _c(G).reshape(batch, n1, n2)
-    g_x1 = torch.empty((batch, n1, D), dtype=ref.dtype, device=ref.device) if need_x1 else None
-    g_x2 = torch.empty((batch, n2, D), dtype=ref.dtype, device=ref.device) if need_x2 else None
-    if sym:
-        if n1 != n2 or sx1 != sx2 or not (need_x1 and need_x2):
-            raise BackendError('matern_build_bwd: sym needs x1 and x2 of one shape and both gradients')
-        g_x2 = g_x1
-    g_ls = torch.empty((batch, D), dtype=ref.dtype, device=ref.device)
-    g_os = torch.empty((batch,), dtype=ref.dtype, device=ref.device)
-    lib = _lib.load()
-    ws = _ws(lib.nsgp_matern_build_bwd_workspace(batch, n1, n2, D, ref.element_size()), ref.device)
-    _lib.call(f'nsgp_matern_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls), _p(os_), batch, n1, n2, D, sx1, sx2, nu2,
-              _p(G), n2, n1 * n2, _p(g_x1), _p(g_x2), _p(g_ls), _p(g_os), _p(ws), ws.numel(), _stream())
-    return g_x1, g_x2, g_ls, g_os
+    return _ard_build_bwd('matern', (_nu2(nu),), x1, x2, ls, os_, G, need_x1, need_x2, sym)
 
 
 # --------------------------------------------------------------------------------------------
@@ -333,16 +326,8 @@ def _rbfper_args(x1, x2, ls_rbf, ls_per, period, os_):
         os_ = _c(os_.reshape(-1))
         if os_.shape[0] != batch:
             raise BackendError('rbf_periodic_build: os must be (batch,)')
-
-    def prep(x):
-        if x.dim() == 2 and x.shape[1] == D:
-            return _c(x), x.shape[0], 0
-        if x.dim() == 3 and x.shape[0] == batch and x.shape[2] == D:
-            x = _c(x)
-            return x, x.shape[1], x.shape[1] * D
-        raise BackendError(f'rbf_periodic_build: x shape {tuple(x.shape)} vs batch {batch}, D {D}')
-    x1, n1, sx1 = prep(x1)
-    x2, n2, sx2 = prep(x2)
+    x1, n1, sx1 = _shared_or_batched(x1, batch, D, 'rbf_periodic_build')
+    x2, n2, sx2 = _shared_or_batched(x2, batch, D, 'rbf_periodic_build')
     return ref, x1, x2, ls_rbf, ls_per, period, os_, batch, n1, n2, D, sx1, sx2
 
 
@@ -1058,6 +1043,21 @@ class GibbsKernelFn(torch.autograd.Function):
                 g_osr, g_diag)
 
 
+def _sum_shared(g_x, x, needed):
+    """Per-batch input gradient (batch,n,D) -> gradient of x: summed over the batch when x:(n,D) was shared."""
+    if not needed:
+        return None
+    return g_x.sum(0) if x.dim() == 2 else g_x
+
+
+def _ard_fn_backward(ctx, build_bwd, extra, G):
+    """backward of the stationary ARD Functions (saved: x1, x2, ls, os_): the gradients of those four inputs."""
+    x1, x2, ls, os_ = ctx.saved_tensors
+    n1g, n2g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    g_x1, g_x2, g_ls, g_os = build_bwd(x1, x2, ls, os_, *extra, G, need_x1=n1g, need_x2=n2g)
+    return _sum_shared(g_x1, x1, n1g), _sum_shared(g_x2, x2, n2g), g_ls.reshape(ls.shape), g_os.reshape(os_.shape)
+
+
 class RbfKernelFn(torch.autograd.Function):
     """K[b] = os[b] RBF-ARD(x1, x2; ls[b]) + diag_add I   (gpytorch ScaleKernel(RBFKernel))."""
 
@@ -1068,14 +1068,7 @@ class RbfKernelFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, G):
-        x1, x2, ls, os_ = ctx.saved_tensors
-        n1g, n2g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        g_x1, g_x2, g_ls, g_os = rbf_build_bwd(x1, x2, ls, os_, G, need_x1=n1g, need_x2=n2g)
-        if n1g and x1.dim() == 2:
-            g_x1 = g_x1.sum(0)
-        if n2g and x2.dim() == 2:
-            g_x2 = g_x2.sum(0)
-        return (g_x1 if n1g else None, g_x2 if n2g else None, g_ls.reshape(ls.shape), g_os.reshape(os_.shape), None)
+        return (*_ard_fn_backward(ctx, rbf_build_bwd, (), G), None)
 
 
 class MaternKernelFn(torch.autograd.Function):
@@ -1089,15 +1082,7 @@ class MaternKernelFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, G):
-        x1, x2, ls, os_ = ctx.saved_tensors
-        n1g, n2g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        g_x1, g_x2, g_ls, g_os = matern_build_bwd(x1, x2, ls, os_, ctx.nu, G, need_x1=n1g, need_x2=n2g)
-        if n1g and x1.dim() == 2:
-            g_x1 = g_x1.sum(0)
-        if n2g and x2.dim() == 2:
-            g_x2 = g_x2.sum(0)
-        return (g_x1 if n1g else None, g_x2 if n2g else None, g_ls.reshape(ls.shape), g_os.reshape(os_.shape), None,
-                None)
+        return (*_ard_fn_backward(ctx, matern_build_bwd, (ctx.nu,), G), None, None)
 
 
 class RbfPeriodicKernelFn(torch.autograd.Function):
@@ -1118,11 +1103,7 @@ class RbfPeriodicKernelFn(torch.autograd.Function):
         os_ = rest.pop(0) if ctx.has[1] else None
         n1g, n2g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g_x1, g_x2, g_lr, g_lp, g_pe, g_os = rbf_periodic_build_bwd(x1, x2, ls_rbf, ls_per, period, os_, G, n1g, n2g)
-        if n1g and x1.dim() == 2:
-            g_x1 = g_x1.sum(0)
-        if n2g and x2.dim() == 2:
-            g_x2 = g_x2.sum(0)
-        return (g_x1 if n1g else None, g_x2 if n2g else None,
+        return (_sum_shared(g_x1, x1, n1g), _sum_shared(g_x2, x2, n2g),
                 g_lr.reshape(ls_rbf.shape) if ls_rbf is not None else None, g_lp.reshape(ls_per.shape),
                 g_pe.reshape(period.shape), g_os.reshape(os_.shape) if os_ is not None else None, None)
 

@@ -81,6 +81,35 @@ def test_matern_entry_points_validate_their_arguments_on_the_host():
         assert bad_b(4, 0) == 0 and bad_b(5, 0) == 0 and bad_b(6, 0) == 0
 
 
+def test_rbf_entry_points_validate_their_arguments_on_the_host():
+    """The RBF entry points share their argument checks with the Matern ones; their return codes are the negative
+    1-based index in their OWN signature (no nu2, so K / ldk / G / ldg sit one place earlier).  Safe without a GPU: no
+    call below reaches the device."""
+    import nsgp
+    lib = nsgp.load_library()
+    buf = (ctypes.c_double * 64)()
+    P = lambda o: ctypes.cast(o, ctypes.c_void_p)
+    b = P(buf)
+    #       x1 x2 ls os batch n1 n2 D sx1 sx2 diag_add K ldk sK stream
+    fwd_ok = [b, b, b, b, 1, 4, 4, 2, 0, 0, 0.0, b, 4, 16, None]
+    #       x1 x2 ls os batch n1 n2 D sx1 sx2 G ldg sG g_x1 g_x2 g_ls g_os ws ws_bytes stream
+    bwd_ok = [b, b, b, b, 1, 4, 4, 2, 0, 0, b, 4, 16, b, b, b, b, b, 512, None]
+    for sfx in ('f32', 'f64'):
+        fwd = getattr(lib, f'nsgp_rbf_build_fwd_{sfx}')
+        bwd = getattr(lib, f'nsgp_rbf_build_bwd_{sfx}')
+        bad_f = lambda i, v: fwd(*[v if k == i else a for k, a in enumerate(fwd_ok)])
+        bad_b = lambda i, v: bwd(*[v if k == i else a for k, a in enumerate(bwd_ok)])
+        for bad in (bad_f, bad_b):
+            assert bad(0, None) == -1 and bad(1, None) == -2 and bad(2, None) == -3 and bad(3, None) == -4
+            assert bad(4, -1) == -5 and bad(5, -1) == -6 and bad(6, -1) == -7
+            assert bad(7, 0) == -8 and bad(7, 9) == -8 and bad(7, -3) == -8
+        assert bad_f(11, None) == -12 and bad_f(12, 3) == -13
+        assert bad_b(10, None) == -11 and bad_b(11, 3) == -12
+        # empty problems: no launch, success
+        assert bad_f(4, 0) == 0 and bad_f(5, 0) == 0 and bad_f(6, 0) == 0
+        assert bad_b(4, 0) == 0 and bad_b(5, 0) == 0 and bad_b(6, 0) == 0
+
+
 def test_matern_kernel_construction_follows_gpytorch():
     from nsgp.gp.kernels import MaternKernel, ScaleKernel
     for nu in (2.0, 0.0, 3.5, 1.0):
