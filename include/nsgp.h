@@ -164,9 +164,23 @@ int nsgp_ps2d_build_bwd_f64(const double* x1, const double* x2, const double* si
 #define NSGP_GEMM_NO_SPLITK 32  /* never split the inner dimension (no workspace needed) */
 #define NSGP_GEMM_C_HALFDIAG 128 /* the diagonal of alpha*op(A)*op(B) is halved before beta*C is added (Phi of the
                                    Cholesky backward: tril with halved diagonal, without a pass of its own) */
-#define NSGP_GEMM_C_NOFILL  64  /* with C_LOWER: leave the strict upper triangle of C untouched (the consumer reads C
-                                   through a LOWER operand flag, which never loads it) -- no memset nodes */
+#define NSGP_GEMM_C_NOFILL  64  /* with C_LOWER: the strict upper triangle of C is UNSPECIFIED afterwards (the consumer reads
+                                   C through a LOWER operand flag, which never loads it) -- no memset nodes.  A single-pass
+                                   launch leaves it untouched; a split-K launch with beta == 0 still writes zeros there. */
+/* C_LOWER with beta != 0: the lower triangle is alpha*op(A)*op(B) + beta*C; the strict upper triangle of C is left as it
+ * was (neither scaled by beta nor zeroed), with or without C_NOFILL, split or not. */
 size_t nsgp_gemm_workspace(int64_t M, int64_t N, int64_t K, int64_t nb1, int64_t nb2, int elem_size, int flags);
+/* Host-side query (no GPU is touched, like nsgp_gemm_workspace): the launch nsgp_gemm_f32/f64 would make for a plain product of
+ * this shape, computed by the code the launch itself runs (the NSGP_GEMM_* environment switches are read the same way).
+ * vec_a / vec_b: the operand qualifies for 16-byte vector loads (unit stride along its contiguous direction, the other stride
+ * and both batch strides multiples of 4, base pointer aligned to 4 elements); mode_a / mode_b: 0 = contiguous along k,
+ * 1 = contiguous along m (n) -- they select the kernel instantiation and are echoed.
+ * out[NSGP_GEMM_PLAN_FIELDS]: 0 tile rows, 1 tile columns, 2 K-slices (ksplit), 3 k per slice (kper), 4 whole (the variant
+ * without bounds code), 5 chunked XCD placement of a split launch (0/1), 6 batch_perm (0..3), 7 grid x, 8 grid y,
+ * 9 mode_a, 10 mode_b.  M == 0 or N == 0: all zero (nothing is launched).  Returns 0, or -(index of the bad argument). */
+#define NSGP_GEMM_PLAN_FIELDS 11
+int nsgp_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t nb1, int64_t nb2, int elem_size, int flags,
+                   int vec_a, int vec_b, int mode_a, int mode_b, int32_t* out);
 int nsgp_gemm_f32(int64_t M, int64_t N, int64_t K, float alpha,
                   const float* A, int64_t sam, int64_t sak, int64_t sa1, int64_t sa2,
                   const float* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2,

@@ -1091,6 +1091,81 @@ template <typename T> Plan make_plan(int64_t M, int64_t N, int64_t K, int64_t nb
     return p;
 }
 
+// Launch order of one plan: tile counts, the grid, the tile-order remap the kernel applies (xcd_group / xcd_chunk /
+// batch_perm, each "speed only") and whether the variant without bounds code (EDGE = 0) runs.  gemm_impl launches what this
+// returns and nsgp_gemm_plan reports it; nothing here touches the GPU.  plain: no fused epilogue / operand scaling.
+struct Order {
+    int bm, bn, bk;               // tile rows, tile columns, K-tile depth
+    int64_t tiles_m, tiles_n;
+    int64_t grid_x, grid_y;
+    int xcd_group, xcd_chunk, batch_perm;
+    bool whole;
+};
+
+template <typename T>
+Order plan_order(const Plan& p, int64_t M, int64_t N, int64_t K, int64_t nb, int flags, bool plain, int vecA, int vecB) {
+    Order o;
+    const int64_t bmn = p.big ? 128 : 64;
+    o.bm = (int)bmn;
+    o.bn = p.narrow ? 64 : (int)bmn;
+    o.bk = bmn == 128 ? 32 : ((sizeof(T) == 8 && plain) ? NSGP_F64_BK : 16);
+    o.tiles_m = cdiv64(M, bmn);
+    o.tiles_n = cdiv64(N, o.bn);
+    const int64_t ngrid = (flags & NSGP_GEMM_C_LOWER) ? active_tiles(M, N, bmn, flags) : o.tiles_m * o.tiles_n;
+    int64_t ngrid_x = ngrid, ngrid_y = nb * p.ksplit;
+    o.xcd_group = 0;
+    o.xcd_chunk = 0;
+    o.batch_perm = 0;
+    const char* no_xcd = getenv("NSGP_GEMM_NO_XCD");              // A/B switches for tools/gemm_bench.py
+    const bool xcd_ok = !(no_xcd && no_xcd[0] == '1');
+    // The column-panel-grouped order is OFF by default: it cuts the fabric traffic of the projections ~3x, but the
+    // hardware deals workgroups to the XCDs in strict rotation, so tiles of unequal length in flight stall the
+    // dispatcher (measured: 611 us grouped vs 472 us in the row-major longest-first order, M=1024, n=40960).
+    const char* grp = getenv("NSGP_GEMM_XCD_GROUP");
+    const int grp_rows = grp ? atoi(grp) : 0;                       // 1: half the tile rows per group; r > 1: r rows per group
+    const bool group_ok = grp_rows >= 1;
+    if (xcd_ok && group_ok && !(flags & NSGP_GEMM_C_LOWER) && p.ksplit == 1 && o.tiles_n >= 16 && o.tiles_m <= 64 &&
+        !(flags & (NSGP_GEMM_B_LOWER | NSGP_GEMM_B_UPPER))) {
+        const bool triA = flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER);
+        int R = (int)o.tiles_m;
+        if (triA && o.tiles_m >= 4 && o.tiles_m % 2 == 0) R = (int)o.tiles_m / 2;     // long rows first, short rows last
+        if (grp_rows > 1 && o.tiles_m % grp_rows == 0) R = grp_rows;
+        o.xcd_group = R;
+        ngrid_x = 8 * (o.tiles_m / R) * (cdiv64(o.tiles_n, 8) * R);
+    } else if (xcd_ok && p.ksplit > 1 && ngrid * ngrid_y >= 64) {
+        const int64_t total = ngrid * ngrid_y;
+        o.xcd_chunk = (int)cdiv64(total, 8);
+        // the launch keeps its (tiles, batch x slices) shape; workgroups past `total` after the remap exit at once
+        ngrid_y = cdiv64(8 * (int64_t)o.xcd_chunk, ngrid);
+    } else if (p.ksplit == 1 && nb > 1 && (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER | NSGP_GEMM_B_LOWER |
+                                                     NSGP_GEMM_B_UPPER | NSGP_GEMM_C_LOWER))) {
+        // batched triangular launch that fits one round of resident workgroups: complementary tile orders per batch element
+        const int64_t slots = 256 * (p.big ? (p.narrow ? 3 : 2) : (sizeof(T) == 4 ? 6 : 3));
+        const char* bpe = getenv("NSGP_GEMM_BATCH_PERM");            // A/B switch (default on)
+        // (more rounds: batch element fastest -- hidden layer, n = 4096 x 2 GPs: 234 -> 225 us for the forward pair)
+        if (!(bpe && bpe[0] == '0')) o.batch_perm = (ngrid * ngrid_y <= slots) ? 1 : ((bpe && bpe[0] == '1') ? 0 : 2);
+    } else if (p.ksplit == 1 && nb == 1 && (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER | NSGP_GEMM_B_LOWER |
+                                                      NSGP_GEMM_B_UPPER | NSGP_GEMM_C_LOWER))) {
+        const int64_t slots = 256 * (p.big ? (p.narrow ? 3 : 2) : (sizeof(T) == 4 ? 6 : 3));
+        const char* bpe = getenv("NSGP_GEMM_BATCH_PERM");
+        if (ngrid > 256 && ngrid <= slots && !(bpe && bpe[0] == '0')) o.batch_perm = 3;       // snake (see the kernel)
+    }
+    o.grid_x = ngrid_x;
+    o.grid_y = ngrid_y;
+    // whole, vector-loadable tiles everywhere -> the variant without bounds code (EDGE = 0)
+    o.whole = vecA && vecB && M % o.bm == 0 && N % o.bn == 0 && K % o.bk == 0 && p.kper % o.bk == 0;
+    return o;
+}
+
+// what nsgp_gemm_plan reports (include/nsgp.h): the plan and order of a plain product
+template <typename T>
+void gemm_plan_fill(int64_t M, int64_t N, int64_t K, int64_t nb, int flags, int vec_a, int vec_b, int32_t* out) {
+    const Plan p = make_plan<T>(M, N, K, nb, flags);
+    const Order o = plan_order<T>(p, M, N, K, nb, flags, true, vec_a, vec_b);
+    out[0] = o.bm; out[1] = o.bn; out[2] = (int32_t)p.ksplit; out[3] = (int32_t)p.kper; out[4] = o.whole;
+    out[5] = o.xcd_chunk > 0; out[6] = o.batch_perm; out[7] = (int32_t)o.grid_x; out[8] = (int32_t)o.grid_y;
+}
+
 template <typename T>
 int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam, int64_t sak, int64_t sa1,
               int64_t sa2, const T* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2, T beta, T* C,
@@ -1127,11 +1202,10 @@ int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam,
         slabs = (T*)ws;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int64_t bmn = p.big ? 128 : 64;
-    g.tiles_m = cdiv64(M, bmn);
-    g.tiles_n = cdiv64(N, p.narrow ? 64 : bmn);
+    const Order o = plan_order<T>(p, M, N, K, nb, flags, !has_epi, g.vecA, g.vecB);
+    g.tiles_m = o.tiles_m;
+    g.tiles_n = o.tiles_n;
     if (g.tiles_m * g.tiles_n > 2147483647LL || nb * g.ksplit > 65535) return -24;
-    const int64_t ngrid = (flags & NSGP_GEMM_C_LOWER) ? active_tiles(M, N, bmn, flags) : g.tiles_m * g.tiles_n;
     if ((flags & NSGP_GEMM_C_LOWER) && !(flags & NSGP_GEMM_C_NOFILL) && g.ksplit == 1 && beta == T(0)) {
         // the strictly-upper tiles are not launched: keep the "strict upper triangle is zero" contract
         // (the split-K reduce kernel writes those zeros itself)
@@ -1142,55 +1216,19 @@ int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam,
                 if (e != hipSuccess) return (int)e;
             }
     }
-    int64_t ngrid_x = ngrid, ngrid_y = nb * g.ksplit;
-    g.xcd_group = 0;
-    g.xcd_chunk = 0;
-    g.batch_perm = 0;
+    const int64_t ngrid_x = o.grid_x, ngrid_y = o.grid_y;
+    g.xcd_group = o.xcd_group;
+    g.xcd_chunk = o.xcd_chunk;
+    g.batch_perm = o.batch_perm;
     g.part_rows = epi ? epi->part_rows : 0;
     g.nbk = (int)(nb * g.ksplit);
-    const char* no_xcd = getenv("NSGP_GEMM_NO_XCD");              // A/B switches for tools/gemm_bench.py
-    const bool xcd_ok = !(no_xcd && no_xcd[0] == '1');
-    // The column-panel-grouped order is OFF by default: it cuts the fabric traffic of the projections ~3x, but the
-    // hardware deals workgroups to the XCDs in strict rotation, so tiles of unequal length in flight stall the
-    // dispatcher (measured: 611 us grouped vs 472 us in the row-major longest-first order, M=1024, n=40960).
-    const char* grp = getenv("NSGP_GEMM_XCD_GROUP");
-    const int grp_rows = grp ? atoi(grp) : 0;                       // 1: half the tile rows per group; r > 1: r rows per group
-    const bool group_ok = grp_rows >= 1;
-    if (xcd_ok && group_ok && !(flags & NSGP_GEMM_C_LOWER) && g.ksplit == 1 && g.tiles_n >= 16 && g.tiles_m <= 64 &&
-        !(flags & (NSGP_GEMM_B_LOWER | NSGP_GEMM_B_UPPER))) {
-        const bool triA = flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER);
-        int R = (int)g.tiles_m;
-        if (triA && g.tiles_m >= 4 && g.tiles_m % 2 == 0) R = (int)g.tiles_m / 2;     // long rows first, short rows last
-        if (grp_rows > 1 && g.tiles_m % grp_rows == 0) R = grp_rows;
-        g.xcd_group = R;
-        ngrid_x = 8 * (g.tiles_m / R) * (cdiv64(g.tiles_n, 8) * R);
-    } else if (xcd_ok && g.ksplit > 1 && ngrid * ngrid_y >= 64) {
-        const int64_t total = ngrid * ngrid_y;
-        g.xcd_chunk = (int)cdiv64(total, 8);
-        // the launch keeps its (tiles, batch x slices) shape; workgroups past `total` after the remap exit at once
-        ngrid_y = cdiv64(8 * (int64_t)g.xcd_chunk, ngrid);
-    } else if (g.ksplit == 1 && nb > 1 && (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER | NSGP_GEMM_B_LOWER |
-                                                     NSGP_GEMM_B_UPPER | NSGP_GEMM_C_LOWER))) {
-        // batched triangular launch that fits one round of resident workgroups: complementary tile orders per batch element
-        const int64_t slots = 256 * (p.big ? (p.narrow ? 3 : 2) : (sizeof(T) == 4 ? 6 : 3));
-        const char* bpe = getenv("NSGP_GEMM_BATCH_PERM");            // A/B switch (default on)
-        // (more rounds: batch element fastest -- hidden layer, n = 4096 x 2 GPs: 234 -> 225 us for the forward pair)
-        if (!(bpe && bpe[0] == '0')) g.batch_perm = (ngrid * ngrid_y <= slots) ? 1 : ((bpe && bpe[0] == '1') ? 0 : 2);
-    } else if (g.ksplit == 1 && nb == 1 && (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER | NSGP_GEMM_B_LOWER |
-                                                      NSGP_GEMM_B_UPPER | NSGP_GEMM_C_LOWER))) {
-        const int64_t slots = 256 * (p.big ? (p.narrow ? 3 : 2) : (sizeof(T) == 4 ? 6 : 3));
-        const char* bpe = getenv("NSGP_GEMM_BATCH_PERM");
-        if (ngrid > 256 && ngrid <= slots && !(bpe && bpe[0] == '0')) g.batch_perm = 3;       // snake (see the kernel)
-    }
     dim3 grid((unsigned)ngrid_x, (unsigned)ngrid_y, 1);
     Epi ep{};
     if (epi) ep = *epi;
     if (tiles_m_out) *tiles_m_out = g.tiles_m;
     const int ekind = ep.kind, eks = ep.ks != nullptr;
     if (ekind != 0 && (g.ksplit != 1 || beta != T(0) || (flags & (NSGP_GEMM_C_LOWER | NSGP_GEMM_C_HALFDIAG)))) return -30;
-    const int64_t bnn = p.narrow ? 64 : bmn, bkk = (bmn == 128 ? 32 : ((sizeof(T) == 8 && ekind == 0 && !eks) ? NSGP_F64_BK : 16));
-    // whole, vector-loadable tiles everywhere -> the variant without bounds code (EDGE = 0)
-    const bool whole = g.vecA && g.vecB && M % bmn == 0 && N % bnn == 0 && K % bkk == 0 && g.kper % bkk == 0;
+    const bool whole = o.whole;                      // whole, vector-loadable tiles everywhere -> the variant without bounds code
     // launch<BM, BN, MA, MB, EP, KS>()  (the PF template slot, round 1's separate two-tiles-in-flight loop, is always 0 now)
     auto launch = [&](auto bm_c, auto bn_c, auto ma_c, auto mb_c, auto ep_c, auto ks_c) {
         constexpr int BM_ = decltype(bm_c)::value, BN_ = decltype(bn_c)::value, MA = decltype(ma_c)::value,
@@ -1455,6 +1493,24 @@ size_t nsgp_gemm_workspace(int64_t M, int64_t N, int64_t K, int64_t nb1, int64_t
     const int64_t nb = nb1 * nb2;
     const Plan p = elem_size == 4 ? make_plan<float>(M, N, K, nb, flags) : make_plan<double>(M, N, K, nb, flags);
     return p.ksplit > 1 ? (size_t)p.ksplit * nb * M * N * elem_size : 0;
+}
+
+int nsgp_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t nb1, int64_t nb2, int elem_size, int flags, int vec_a, int vec_b,
+                   int mode_a, int mode_b, int32_t* out) {
+    if (M < 0) return -1; if (N < 0) return -2; if (K < 0) return -3;
+    if (nb1 < 1) return -4; if (nb2 < 1) return -5;
+    if (elem_size != 4 && elem_size != 8) return -6;
+    if ((flags & NSGP_GEMM_A_LOWER) && (flags & NSGP_GEMM_A_UPPER)) return -7;
+    if ((flags & NSGP_GEMM_B_LOWER) && (flags & NSGP_GEMM_B_UPPER)) return -7;
+    if ((mode_a | 1) != 1) return -10; if ((mode_b | 1) != 1) return -11;
+    if (!out) return -12;
+    for (int i = 0; i < NSGP_GEMM_PLAN_FIELDS; ++i) out[i] = 0;
+    if (M == 0 || N == 0) return 0;                      // nsgp_gemm_* launches nothing
+    const int64_t nb = nb1 * nb2;
+    if (elem_size == 4) gemm_plan_fill<float>(M, N, K, nb, flags, vec_a != 0, vec_b != 0, out);
+    else gemm_plan_fill<double>(M, N, K, nb, flags, vec_a != 0, vec_b != 0, out);
+    out[9] = mode_a; out[10] = mode_b;
+    return 0;
 }
 
 int nsgp_gemm_f32(int64_t M, int64_t N, int64_t K, float alpha, const float* A, int64_t sam, int64_t sak,

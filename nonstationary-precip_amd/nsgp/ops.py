@@ -427,10 +427,24 @@ def set_gemm_timer(timer):
     _gemm_timer = timer
 
 
-def gemm(A, B, ta=False, tb=False, alpha=1.0, beta=0.0, out=None, flags=0):
-    """out = alpha * op(A) @ op(B) + beta * out on the matrix cores.  2-D or batched 3-D operands
-    (a 2-D operand broadcasts against a 3-D one)."""
-    ref = _chk(A, B, out)
+class GemmPlan(NamedTuple):
+    """The launch nsgp_gemm_* makes for a product (include/nsgp.h, nsgp_gemm_plan): the fields of its `out` array."""
+    tile_m: int
+    tile_n: int
+    ksplit: int
+    kper: int
+    whole: int
+    xcd_chunk: int
+    batch_perm: int
+    grid_x: int
+    grid_y: int
+    mode_a: int
+    mode_b: int
+
+
+def _gemm_operands(A, B, ta, tb, out):
+    """Views, sizes, strides and the output of gemm(); shared with gemm_plan so that both see the same operands."""
+    ref = A
     A, M, K, sam, sak, nba, sba = _mat_view(A, ta)
     B, K2, N, sbk, sbn, nbb, sbb = _mat_view(B, tb)
     if K != K2:
@@ -444,13 +458,40 @@ def gemm(A, B, ta=False, tb=False, alpha=1.0, beta=0.0, out=None, flags=0):
         sbb = 0
     batched = A.dim() == 3 or B.dim() == 3
     shape = (nb, M, N) if batched else (M, N)
+    if out is not None and (tuple(out.shape) != shape or not out.is_contiguous()):
+        raise BackendError(f'gemm: out must be contiguous {shape}, got {tuple(out.shape)}')
+    return ref, shape, A, M, K, sam, sak, sba, B, N, sbk, sbn, sbb, nb
+
+
+def gemm_plan(A, B, ta=False, tb=False, flags=0, out=None):
+    """The plan `gemm(A, B, ta, tb, flags=flags, out=out)` launches, as a GemmPlan.  Host-side only: nothing is launched and
+    no GPU is needed (CPU tensors of the same layout give the plan of their device twins as far as their base pointers are
+    aligned alike).  mode_* / vec_* are derived from the operand views the way gemm_impl (csrc/gemm.hip) derives them."""
+    _sfx(A)
+    ref, shape, A, M, K, sam, sak, sba, B, N, sbk, sbn, sbb, nb = _gemm_operands(A, B, ta, tb, out)
+    es = ref.element_size()
+
+    def mode_vec(t, s_other, s_k, s_batch):            # s_k: stride along k; s_other: along m (A) or n (B)
+        mode = 0 if s_k == 1 else (1 if s_other == 1 else 0)
+        unit, other = (s_k, s_other) if mode == 0 else (s_other, s_k)
+        return mode, int(unit == 1 and other % 4 == 0 and s_batch % 4 == 0 and t.data_ptr() % (4 * es) == 0)
+    mode_a, vec_a = mode_vec(A, sam, sak, sba)
+    mode_b, vec_b = mode_vec(B, sbn, sbk, sbb)
+    buf = (ctypes.c_int32 * len(GemmPlan._fields))()
+    _lib.call('nsgp_gemm_plan', M, N, K, nb, 1, es, int(flags), vec_a, vec_b, mode_a, mode_b,
+              ctypes.cast(buf, ctypes.c_void_p))
+    return GemmPlan(*buf)
+
+
+def gemm(A, B, ta=False, tb=False, alpha=1.0, beta=0.0, out=None, flags=0):
+    """out = alpha * op(A) @ op(B) + beta * out on the matrix cores.  2-D or batched 3-D operands
+    (a 2-D operand broadcasts against a 3-D one)."""
+    ref = _chk(A, B, out)
+    ref, shape, A, M, K, sam, sak, sba, B, N, sbk, sbn, sbb, nb = _gemm_operands(A, B, ta, tb, out)
     if out is None:
         if beta != 0.0:
             raise BackendError('gemm: beta != 0 needs out')
         out = torch.empty(shape, dtype=ref.dtype, device=ref.device)
-    else:
-        if tuple(out.shape) != shape or not out.is_contiguous():
-            raise BackendError(f'gemm: out must be contiguous {shape}, got {tuple(out.shape)}')
     lib = _lib.load()
     wsb = 0 if (flags & GEMM_NO_SPLITK) else lib.nsgp_gemm_workspace(M, N, K, nb, 1, ref.element_size(), int(flags))
     ws = _ws(wsb, ref.device) if wsb else None

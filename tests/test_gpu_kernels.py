@@ -632,7 +632,9 @@ def test_scalar_total_elbo_terms_match_autograd_of_the_vector_forms(ops, dt):
 def test_gemm_narrow_tiles_for_single_round_triangular_launches(ops, N, ta, flag):
     """M = K = 1024 with a triangular A operand and a grid that fits one round of the 512 slots takes the 128x64 tile
     variant (three workgroups per CU): the hidden layer at one GPU (n = 4096), a rank's last layer at eight (n = 5120),
-    and a ragged width.  float32 against a float64 product of the same (masked) operands."""
+    and a ragged width.  float32 against a float64 product of the same (masked) operands.  Production passes NO_SPLITK
+    (nsgp/svgp.py), and only then do all three widths run the narrow tiles: the plan is asserted, not assumed (without the
+    flag n = 4096 and 5120 split K on 128x128 tiles; that launch is held to the same error below)."""
     g = _g(5 + N)
     M = 1024
     A = torch.randn(M, M, generator=g)
@@ -640,9 +642,14 @@ def test_gemm_narrow_tiles_for_single_round_triangular_launches(ops, N, ta, flag
     junk = torch.triu(torch.full((M, M), 3.0), 1)              # the ignored triangle holds garbage
     Ain = torch.tril(A) + junk                                 # stored lower; with ta its transpose (upper) is the operand
     ref = (torch.tril(A).double().t() if ta else torch.tril(A).double()) @ B.double()
-    out = ops.gemm(Ain.cuda(), B.cuda(), ta=ta, flags=getattr(ops, 'GEMM_' + flag))
-    err = float((out.cpu().double() - ref).abs().max()) / float(ref.abs().max())
-    assert err < 2e-6, err
+    for extra in (ops.GEMM_NO_SPLITK, 0):
+        flags = getattr(ops, 'GEMM_' + flag) | extra
+        if extra:
+            plan = ops.gemm_plan(Ain.cuda(), B.cuda(), ta, False, flags)
+            assert (plan.tile_m, plan.tile_n, plan.ksplit) == (128, 64, 1), plan
+        out = ops.gemm(Ain.cuda(), B.cuda(), ta=ta, flags=flags)
+        err = float((out.cpu().double() - ref).abs().max()) / float(ref.abs().max())
+        assert err < 2e-6, err
 
 
 
