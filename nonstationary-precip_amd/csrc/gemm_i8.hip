@@ -30,7 +30,9 @@
 // (5 x 128 + SK x 64) x 32 bytes (28 / 30 KB), images [plane][h][row][16] so that an operand fragment is one
 // conflict-free ds_read_b128 per lane; the stages are filled by LDS-DMA (global_load_lds_dwordx4: a K-step's block is one
 // contiguous run in memory, so no registers are spent on staging; NSGP_I8_DMA=0 builds the register-staged form); the K
-// planes of a K-step stay in registers while the W planes stream through; two workgroups per CU.
+// planes of a K-step stay in registers while the W planes stream through; behind the stages, 1.5 KB for the row scales and
+// the row vector of the tile's 128 rows, which the prologue fetches beside the first stage so that the epilogue reads no
+// global memory; two workgroups per CU (2 x 57.5 / 61.5 KB of the 160 KB LDS, 210 / 253 VGPRs, no scratch).
 #include <cstdlib>
 #include "common.h"
 
@@ -172,14 +174,23 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
     constexpr int A_STAGE = I8_SW * 2 * I8_BM * 16, B_STAGE = SK * 2 * I8_BN * 16;       // 20480 + 8192 bytes
     unsigned char* As = i8_smem;                            // [2][A_STAGE]
     unsigned char* Bs = i8_smem + 2 * A_STAGE;              // [2][B_STAGE]
+    double* Ws = reinterpret_cast<double*>(i8_smem + 2 * (A_STAGE + B_STAGE));           // [128] wsc of the tile's rows
+    float* Rs = reinterpret_cast<float*>(Ws + I8_BM);                                     // [128] rv of the tile's rows
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 32;
     const int64_t bb = blockIdx.y;
     const int tiles_m = (int)(Mp / I8_BM);
-    // Anatomy of the two launches of a headline step (0.441 ms; switches that skipped the MFMAs / the staging / both):
-    // staging alone 0.345, MFMAs + fragment reads alone 0.363, neither -- first-stage latency, barriers, the float64 Horner
-    // epilogue and the stores of 5120 + 1024 short workgroups -- 0.187 ms.  The K loop moves 28 KB into LDS per 112 MFMAs
-    // (2.6 GB per launch, 7.4 TB/s): larger tiles (128 x 128 with eight waves) are the lever, not the tile order.
+    // Anatomy of the two launches of a headline step (0.447 -> 0.374 ms once the epilogue stopped loading from global memory:
+    // 356 -> 292 us for <0,4,5> at n = 40960, 91 -> 82 us for <1,5,6> at b = 2, n = 4096).  Switches that skipped the MFMAs /
+    // the staging / both, measured on the loop before that change (0.441 ms): staging alone 0.345, MFMAs + fragment reads
+    // alone 0.363, neither -- first-stage latency, barriers, the float64 Horner epilogue and the stores of 5120 + 1024 short
+    // workgroups -- 0.187 ms, of which the epilogue's 64 serialised loads per workgroup (the row scale and the row vector
+    // under the per-element bounds test: one branch, one load, one vmcnt(0) each) were the 0.07 ms now gone.  The K loop is
+    // as it was: one K-block of prefetch, vmcnt(0) and a barrier per K-block, 28 KB into LDS per 112 MFMAs (2.6 GB per
+    // launch, 7.4 TB/s).  Not built: a ring of three stages with counted waits (W alone fits three stages twice per CU, 2 x
+    // 61.5 KB, if the Kzx fragments go straight to registers -- whose ordinary loads the compiler waits for with vmcnt(0)
+    // while an LDS-DMA is in flight, so they would have to be issued and counted by hand), and more than one tile per
+    // workgroup.
     // (Tried and dropped: an XCD-grouped order -- workgroup 8 q + x, which the hardware places on XCD x, walking all row tiles of
     // column tiles x, x + 8, ... back to back so that a column tile's Kzx planes enter that L2 once: 0.441 -> 0.534 ms per
     // headline step, like the same experiment on the float32 GEMM.)
@@ -256,14 +267,31 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
     // this wave's rows reach k < m0 + wm0 + 64: the upper wave row has nothing to do in the tile's last two k-blocks
     const int wave_nkb = __builtin_amdgcn_readfirstlane((int)((m0 + wm0 + 64 + I8_BK - 1) / I8_BK));
     const int half = lane >> 5, lr = lane & 31;
+    // The epilogue's operands are fetched here, beside the first stage's cold load, not after the loop: the row scales and
+    // the row vector of the tile's 128 rows go to LDS (zeros for rows >= M and for a null rv), the digit scale of Kzx is
+    // folded by the barrier that publishes the first stage -- the build's slot of k-block 0 for these columns, NaN if the
+    // slot of any k-block this tile reads is NaN.
+    const int64_t gx = (np + 255) >> 8;
+    const double* ks = ksc + bb * KB * gx + (n0 >> 8);
+    const float* rvb = rv ? rv + bb * M : nullptr;
 #if NSGP_I8_DMA
     dma(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
     gload(0);
     sstore(0);
 #endif
-    __syncthreads();
+    // (clamped indices, not branches: the three loads leave together and are waited for once, with the stage)
+    const double kslot = ks[(int64_t)(tid < nkb ? tid : nkb - 1) * gx];
+    const int64_t prow = m0 + (tid & (I8_BM - 1)), crow = prow < M ? prow : M - 1;
+    const double wload = wsc[bb * M + crow];
+    const float rload = rvb ? rvb[crow] : 0.0f;
+    const double wrow = prow < M ? wload : 0.0;
+    const float rrow = prow < M ? rload : 0.0f;
+    if (tid < I8_BM) { Ws[tid] = wrow; Rs[tid] = rrow; }
+#if NSGP_I8_DMA
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    const double kscale = __syncthreads_or(kslot != kslot) ? __builtin_nan("") : ks[0];
     for (int kb = 0; kb < nkb; ++kb) {
         const int buf = kb & 1;
 #if NSGP_I8_DMA
@@ -306,27 +334,26 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
         __syncthreads();                                   // ... and so have everybody else's
     }
 
-    // epilogue: levels -> float64 -> one rounding to float32; column statistics from the float64 values.  The digit scale of
-    // Kzx: the build's slot of k-block 0 for these columns, NaN if the slot of any k-block this tile read is NaN
-    const int64_t gx = (np + 255) >> 8;
-    const double* ks = ksc + bb * KB * gx + (n0 >> 8);
-    const double kslot = tid < nkb ? ks[(int64_t)tid * gx] : 0.0;
-    const double kscale = __syncthreads_or(kslot != kslot) ? __builtin_nan("") : ks[0];
+    // epilogue: levels -> float64 -> one rounding to float32; column statistics from the float64 values.  No global load is
+    // left in it: a load under the per-element `in` made the compiler branch around it and wait for it alone, 64 dependent
+    // round trips per workgroup.
     double sdot = 0.0, ssq = 0.0;
     const int64_t col = n0 + wn0 + lr;
-    const float* rvb = rv ? rv + bb * M : nullptr;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t row = m0 + wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int lrow = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int64_t row = m0 + lrow;
+            const double wr = Ws[lrow];
+            const float rr = Rs[lrow];
             double v = (double)acc[LEV - 1][i][r];
 #pragma unroll
             for (int l = LEV - 2; l >= 0; --l) v = __builtin_fma(v, 0.0078125, (double)acc[l][i][r]);
             const bool in = row < M && col < n;
-            v *= (in ? wsc[bb * M + row] : 0.0) * kscale;
+            v *= (in ? wr : 0.0) * kscale;
             if (in) Y[(bb * M + row) * n + col] = (float)v;
-            sdot += v * ((rvb && in) ? (double)rvb[row] : 0.0);
+            sdot += v * ((rvb && in) ? (double)rr : 0.0);
             ssq += v * v;
         }
     sdot += __shfl_xor(sdot, 32, 64);
@@ -417,7 +444,7 @@ int nsgp_svgp_tri_gemm_colstats_i8(const void* Wd, const double* wscale, const v
     const int64_t Mp = i8_mp(M), np = i8_np(n), KB = i8_kb(M);
     const int64_t tiles_n = np / I8_BN, tiles = (Mp / I8_BM) * tiles_n;
     if (tiles > 2147483647LL || batch > 65535) return -8;
-    const size_t lds = 2 * (size_t)(I8_SW * 2 * I8_BM * 16 + planes * 2 * I8_BN * 16);
+    const size_t lds = 2 * (size_t)(I8_SW * 2 * I8_BM * 16 + planes * 2 * I8_BN * 16) + I8_BM * (sizeof(double) + sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)tiles, (unsigned)batch);
 #define NSGP_I8_PROJ(PP, SS) hipLaunchKernelGGL((i8_proj_kernel<PP, SS, (SS == 5 ? 6 : 5)>), grid, dim3(256), lds, st, (const signed char*)Wd, wscale, \
