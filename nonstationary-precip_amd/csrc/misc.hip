@@ -106,11 +106,15 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     const float step_size = lr / bc1, ibc2 = 1.0f / bc2_sqrt;
     const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i0 >= n) return;
+    // The fused multiply-adds are spelled out: left to the compiler, the float4 branch and the two forms of the scalar
+    // loop each contracted `b2 * vi + ...` and the denominator differently, so a parameter's update depended, in the last
+    // bit, on the alignment of its bucket.  (These are the contractions the float4 branch had.)
     auto upd = [&](float& pi, float gi, float& mi, float& vi) {
+#pragma clang fp contract(off)
         const float gr = gi * gscale;
-        mi = b1 * mi + (1.0f - b1) * gr;
-        vi = b2 * vi + (1.0f - b2) * gr * gr;
-        pi -= step_size * mi / (sqrtf(vi) * ibc2 + eps);
+        mi = __builtin_fmaf(b1, mi, (1.0f - b1) * gr);
+        vi = __builtin_fmaf(b2, vi, ((1.0f - b2) * gr) * gr);
+        pi -= (step_size * mi) / __builtin_fmaf(sqrtf(vi), ibc2, eps);
     };
     const bool vec = (i0 + 3 < n) && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0);
     if (vec) {
