@@ -15,8 +15,8 @@
 //   update workgroups  the rest of the previous panel's rank-64 update (columns beyond the current panel): one
 //                  64x64 lower tile each, ONE K step, all loads issued up front.  They touch no data of the panel
 //                  workgroups, so the update overlaps the next factorisation (look-ahead of depth 1).
-//   n >= 2048      rank-64 updates stay inside a 256-column outer panel; the rest of the trailing matrix is
-//                  updated once per outer panel (K = 256) on the MFMA GEMM.
+//   n > 2048       rank-64 updates stay inside an outer panel of 2048 columns (n <= 4096) or 1024 columns; the rest of
+//                  the trailing matrix is updated once per outer panel (K = its width) on the MFMA GEMM.
 // trtri: invert the 64x64 diagonal blocks (16x16 substitution + MFMA merges), then merge pairs of blocks
 //   bottom-up, X21 = -B^-1 (C A^-1), every level two batched MFMA GEMMs (log2(n/64) levels).
 #include "common.h"
@@ -33,7 +33,7 @@ namespace {
 
 #ifdef NSGP_POTRF_STAMPS
 // Diagnostic build only (tools/probes/potrf_stamps.py): workgroup 0 of matrix 0 records shader-clock stamps at the phase
-// boundaries of panel_body2, one 16-word record per panel launch.  Never in the shipped library.
+// boundaries of panel_body, one 16-word record per panel launch.  Never in the shipped library.
 __device__ unsigned long long* nsgp_pstamp_buf = nullptr;
 __device__ unsigned long long nsgp_pstamp_cap = 0;
 #define NSGP_PSTAMP(i) do { if (pst_on) pst[i] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -154,15 +154,11 @@ constexpr int LDI = SB + 1;
 // Sub-panel step of the 64x64 diagonal block held in LDS (S, leading dimension LDD): ONE wave takes
 // columns [c0, c0+16) with row `lane` in registers, factors them (16 pivots, v_readlane broadcasts),
 // and writes them back.  Lanes < c0 write zeros (upper part of L).
-#ifndef NSGP_POTRF_LDSCOL
-#define NSGP_POTRF_LDSCOL 1
-#endif
 template <typename T, int C0> __device__ __forceinline__ int factor_subpanel(T* S, T* rd, T* cb, int lane) {
     T a[SB];
 #pragma unroll
     for (int j = 0; j < SB; ++j) a[j] = S[lane * LDD + C0 + j];
     int bad = 0;
-#if NSGP_POTRF_LDSCOL
     // (Tried in round 3 and dropped: FOUR pivots at a time -- the pivot rows publish the 4 x 4 diagonal block through LDS, every
     // lane factors it redundantly in registers, solves its own row against it and takes the rank-4 update's multipliers from
     // LDS as broadcast 128-bit reads.  Fewer instructions, but two LDS round trips and a 4-deep rsqrt chain per block: 1630
@@ -209,21 +205,6 @@ template <typename T, int C0> __device__ __forceinline__ int factor_subpanel(T* 
         lprev = lik;
     }
     if (is_pub) rd[lane] = rdv;                                              // 1 / L[p][p], one store for the sub-panel
-#else
-#pragma unroll
-    for (int k = 0; k < SB; ++k) {
-        const int p = C0 + k;
-        const T akk = bcast(a[k], p);
-        if (!(akk > T(0)) && bad == 0) bad = p + 1;
-        const T inv = fast_rsqrt(akk);
-        const T piv = akk * inv;
-        if (lane == 0) rd[p] = inv;                                          // 1 / L[p][p]
-        const T lik = lane == p ? piv : (lane > p ? a[k] * inv : T(0));
-        a[k] = lik;
-#pragma unroll
-        for (int j = k + 1; j < SB; ++j) a[j] -= lik * bcast(lik, C0 + j);
-    }
-#endif
 #pragma unroll
     for (int j = 0; j < SB; ++j) S[lane * LDD + C0 + j] = a[j];
     return bad;
@@ -257,192 +238,46 @@ template <typename T> __device__ __forceinline__ void invert_subblock(const T* S
     for (int i = 0; i < SB; ++i) Dinv[(B0 * SB + i) * LDI + lane] = acc[i];
 }
 
-// FULL 64-wide panel.  grid.x = nslab workgroups of 4 waves, each factors the
-// diagonal block in LDS (redundantly: no grid-wide dependency) -- 4 sub-panels of 16 columns, each factored
-// by wave 0 in registers, the rest of the block updated by all waves with 16x16x4 MFMAs -- invert the four
-// 16x16 diagonal sub-blocks, and solve their own 64-row slab  L21 = A21 L11^-T  by blocked substitution
-// (MFMA updates, multiplication by the 16x16 inverses).  The slab's global loads are issued before the
-// factorisation so their latency is hidden.  Block 0 publishes L11 to the side buffer (other workgroups
-// still read A11); potrf_finalize_kernel copies the factors into place at the end.
-// `pre`: the rank-64 update of the PREVIOUS panel (columns [j0-64, j0)) has not been applied to this block column
-// yet; the workgroup applies it to its own diagonal block and slab first (two 64x64x64 MFMA products on blocks
-// that are loaded together with everything else), so that the previous panel's update of the REST of the
-// trailing matrix can run concurrently in the same launch (potrf_step_kernel).
-template <typename T>
-__device__ __forceinline__ void panel_body(unsigned char* panel_smem, T* __restrict__ A, int64_t n, int64_t lda,
-                                           int64_t sA, int64_t j0, T* __restrict__ wsL, int64_t npanels,
-                                           int32_t* __restrict__ info, int64_t blk, int64_t b, bool pre) {
+// Trailing update of the diagonal block after sub-panel C0: S -= L_c L_c^T on the lower 16x16 tiles right of it, dealt to the
+// four waves.  The panel and the inverse's row-block workgroups both come through here (same arithmetic on the same data);
+// the barrier that ends the update stays with the caller.
+template <typename T, int C0> __device__ __forceinline__ void diag_trail_update(T* S, int w, int lane) {
     typedef Mma16<T> MM;
-    typedef typename MM::acc_t acc_t;
-    T* S = reinterpret_cast<T*>(panel_smem);            // [64][LDD]   diagonal block -> L11
-    T* Xs = S + NB * LDD;                               // [64][LDD]   this workgroup's slab
-    T* Dinv = Xs + NB * LDD;                            // [4][16][LDI] inverses of the 16x16 diagonal sub-blocks
-    T* rd = Dinv + 4 * SB * LDI;                        // [64] reciprocal pivots
-    T* Ps = rd + NB;                                    // [64][LDD]   previous panel's L, diagonal-block rows
-    T* Qs = Ps + NB * LDD;                              // [64][LDD]   previous panel's L, slab rows
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    T* Ab = A + b * sA;
-    const int64_t pj = j0 / NB;
-    const int64_t r0 = j0 + NB + blk * NB;
-    const int rows = r0 >= n ? 0 : (int)((n - r0) < NB ? (n - r0) : NB);
-    const int fm = lane & 15, fk = lane >> 4;            // MFMA operand lane -> (m|n, k)
-    // global -> LDS: wave w takes rows [16w, 16w+16) of every block, one coalesced 64-element row per
-    // instruction; the slab rows stay in registers until the factorisation is done.
-    T xr[SB];
-    {
-        T dr[SB], pr[SB], qr[SB];                        // loads first, LDS stores after (one exposed latency)
+    const int fm = lane & 15, fk = lane >> 4;
+    constexpr int B0 = C0 / SB;
+    constexpr int NT = (3 - B0) * (4 - B0) / 2;          // lower tiles of the trailing block
+    for (int q = w; q < NT; q += 4) {
+        int ti = B0 + 1, tj = B0 + 1, c = q;
+        while (c > ti - (B0 + 1)) { c -= ti - B0; ++ti; }
+        tj = B0 + 1 + c;
+        typename MM::acc_t acc;
 #pragma unroll
-        for (int i = 0; i < SB; ++i) dr[i] = Ab[(j0 + w * SB + i) * lda + j0 + lane];
-#pragma unroll
-        for (int i = 0; i < SB; ++i) {                   // clamped row: unconditional loads (no branch per load)
-            const int64_t rr = r0 + w * SB + i;
-            xr[i] = Ab[(rr < n ? rr : n - 1) * lda + j0 + lane];
-        }
-        if (pre) {
-#pragma unroll
-            for (int i = 0; i < SB; ++i) {
-                const int64_t rr = r0 + w * SB + i;
-                pr[i] = Ab[(j0 + w * SB + i) * lda + j0 - NB + lane];
-                qr[i] = Ab[(rr < n ? rr : n - 1) * lda + j0 - NB + lane];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SB; ++i) { keep(dr[i]); keep(xr[i]); }
-        if (pre) {
-#pragma unroll
-            for (int i = 0; i < SB; ++i) { keep(pr[i]); keep(qr[i]); }
-        }
-#pragma unroll
-        for (int i = 0; i < SB; ++i) {
-            S[(w * SB + i) * LDD + lane] = dr[i];
-            xr[i] = (w * SB + i) < rows ? xr[i] : T(0);
-            if (pre) {
-                Ps[(w * SB + i) * LDD + lane] = pr[i];
-                Qs[(w * SB + i) * LDD + lane] = (w * SB + i) < rows ? qr[i] : T(0);
-            }
-        }
-    }
-    __syncthreads();
-    if (pre) {                                           // S -= P P^T : wave w owns rows [16w, 16w+16)
-        acc_t acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][r] = S[(w * SB + MM::crow(r, lane)) * LDD + t * SB + fm];
-#pragma unroll
-        for (int kk = 0; kk < NB / 4; ++kk) {
-            const T av = -Ps[(w * SB + fm) * LDD + 4 * kk + fk];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = MM::mma(av, Ps[(t * SB + fm) * LDD + 4 * kk + fk], acc[t]);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) S[(w * SB + MM::crow(r, lane)) * LDD + t * SB + fm] = acc[t][r];
-        __syncthreads();
-    }
-
-    int bad = 0;
-#define NSGP_SUBPANEL(C0)                                                                             \
-    {                                                                                                 \
-        constexpr int B0 = C0 / SB;                                                                   \
-        if (w == 0) { const int bd = factor_subpanel<T, C0>(S, rd, Qs + NB * LDD, lane); if (bad == 0) bad = bd; }   \
-        else if (w == 1 && B0 > 0) invert_subblock<T>(S, rd, Dinv, B0 - 1, lane);  /* overlaps the factor */ \
-        __syncthreads();                                                                              \
-        constexpr int NT = (3 - B0) * (4 - B0) / 2;      /* lower tiles of the trailing block */      \
-        for (int q = w; q < NT; q += 4) {                                                             \
-            int ti = B0 + 1, tj = B0 + 1, c = q;                                                      \
-            while (c > ti - (B0 + 1)) { c -= ti - B0; ++ti; }                                         \
-            tj = B0 + 1 + c;                                                                          \
-            acc_t acc;                                                                                \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r)                                             \
-                acc[r] = S[(ti * SB + MM::crow(r, lane)) * LDD + tj * SB + fm];                       \
-            _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) {                                        \
-                const T av = -S[(ti * SB + fm) * LDD + C0 + 4 * kk + fk];                             \
-                const T bv = S[(tj * SB + fm) * LDD + C0 + 4 * kk + fk];                              \
-                acc = MM::mma(av, bv, acc);                                                           \
-            }                                                                                         \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r)                                             \
-                S[(ti * SB + MM::crow(r, lane)) * LDD + tj * SB + fm] = acc[r];                       \
-        }                                                                                             \
-        if (NT > 0) __syncthreads();                                                                  \
-    }
-    NSGP_SUBPANEL(0)
-    NSGP_SUBPANEL(16)
-    NSGP_SUBPANEL(32)
-    NSGP_SUBPANEL(48)
-#undef NSGP_SUBPANEL
-
-    if (w == 1) invert_subblock<T>(S, rd, Dinv, 3, lane);
-#pragma unroll
-    for (int i = 0; i < SB; ++i) Xs[(w * SB + i) * LDD + lane] = xr[i];
-    __syncthreads();
-    if (pre && rows > 0) {                               // X -= Q P^T on this wave's strip (rows stay wave-private)
-        acc_t acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][r] = Xs[(w * SB + MM::crow(r, lane)) * LDD + t * SB + fm];
-#pragma unroll
-        for (int kk = 0; kk < NB / 4; ++kk) {
-            const T av = -Qs[(w * SB + fm) * LDD + 4 * kk + fk];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = MM::mma(av, Ps[(t * SB + fm) * LDD + 4 * kk + fk], acc[t]);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Xs[(w * SB + MM::crow(r, lane)) * LDD + t * SB + fm] = acc[t][r];
-    }
-    __syncthreads();
-
-    if (blk == 0) {
-        T* dst = wsL + (b * npanels + pj) * NB * NB;
-#pragma unroll
-        for (int i = 0; i < SB; ++i) dst[(w * SB + i) * NB + lane] = S[(w * SB + i) * LDD + lane];
-        // the first panel initialises info (no memset launch); later panels record only the first failure
-        if (tid == 0) {
-            if (j0 == 0) info[b] = bad ? (int32_t)bad : 0;
-            else if (bad && info[b] == 0) info[b] = (int32_t)(j0 + bad);
-        }
-    }
-    if (rows == 0) return;                               // workgroup-uniform
-
-    // slab strip of wave w: rows [16w, 16w+16).  X_cb = (A_cb - sum_{kb<cb} X_kb L[cb][kb]^T) Dinv_cb^T
-    T* Xw = Xs + (w * SB) * LDD;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-        acc_t acc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = Xw[MM::crow(r, lane) * LDD + cb * SB + fm];
-#pragma unroll
-        for (int kb = 0; kb < cb; ++kb)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const T av = -Xw[fm * LDD + kb * SB + 4 * kk + fk];
-                const T bv = S[(cb * SB + fm) * LDD + kb * SB + 4 * kk + fk];
-                acc = MM::mma(av, bv, acc);
-            }
-        __syncthreads();                                 // (uniform) all reads of the strip issued before it is overwritten
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Xw[MM::crow(r, lane) * LDD + cb * SB + fm] = acc[r];
-        __syncthreads();
-        acc_t y = {T(0), T(0), T(0), T(0)};
+        for (int r = 0; r < 4; ++r) acc[r] = S[(ti * SB + MM::crow(r, lane)) * LDD + tj * SB + fm];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            const T av = Xw[fm * LDD + cb * SB + 4 * kk + fk];
-            const T bv = Dinv[(cb * SB + fm) * LDI + 4 * kk + fk];
-            y = MM::mma(av, bv, y);
+            const T av = -S[(ti * SB + fm) * LDD + C0 + 4 * kk + fk];
+            const T bv = S[(tj * SB + fm) * LDD + C0 + 4 * kk + fk];
+            acc = MM::mma(av, bv, acc);
         }
-        __syncthreads();
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Xw[MM::crow(r, lane) * LDD + cb * SB + fm] = y[r];
-        __syncthreads();
+        for (int r = 0; r < 4; ++r) S[(ti * SB + MM::crow(r, lane)) * LDD + tj * SB + fm] = acc[r];
     }
-#pragma unroll
-    for (int i = 0; i < SB; ++i)
-        if (w * SB + i < rows) Ab[(r0 + w * SB + i) * lda + j0 + lane] = Xw[i * LDD + lane];
 }
+
+// Dynamic LDS of the step kernels as panel_body and prow_body carve it (syrk_body and pupd_body use the first two blocks).
+template <typename T> struct PanelLds {
+    T* S;       // [64][LDD]    diagonal block -> L11
+    T* Xs;      // [64][LDD]    the workgroup's own block: its slab of the panel, or its chunk of W's row block
+    T* Dinv;    // [4][16][LDI] inverses of the 16x16 diagonal sub-blocks
+    T* rd;      // [64]         reciprocal pivots
+    T* Ps;      // [64][LDD]    previous panel's L, diagonal-block rows
+    T* Qs;      // [64][LDD]    previous panel's L, slab rows; or W[j-1][c] (K x N)
+    T* cb;      // [2][16]      factor_subpanel's pivot-column exchange buffers
+    static constexpr size_t bytes = (4 * (size_t)NB * LDD + 4 * SB * LDI + NB + 2 * SB) * sizeof(T);
+    __device__ __forceinline__ explicit PanelLds(unsigned char* smem)
+        : S(reinterpret_cast<T*>(smem)), Xs(S + NB * LDD), Dinv(Xs + NB * LDD), rd(Dinv + 4 * SB * LDI), Ps(rd + NB),
+          Qs(Ps + NB * LDD), cb(Qs + NB * LDD) {}
+};
 
 // LDS traffic written and re-read by ONE wave (other lanes): the LDS executes a wave's instructions in order, the fence
 // only stops the compiler from moving them across (and drains lgkmcnt)
@@ -451,26 +286,18 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// C(16 x 16 tile at Ct) -= A(16 rows at Ar) B(16 rows at Br)^T over K = 64, everything in LDS with leading dimension LDD
-template <typename T>
-__device__ __forceinline__ void rank64_tile(T* Ct, const T* Ar, const T* Br, int lane) {
-    typedef Mma16<T> MM;
-    const int fm = lane & 15, fk = lane >> 4;
-    typename MM::acc_t acc;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = Ct[MM::crow(r, lane) * LDD + fm];
-#pragma unroll
-    for (int kk = 0; kk < NB / 4; ++kk) acc = MM::mma(-Ar[fm * LDD + 4 * kk + fk], Br[fm * LDD + 4 * kk + fk], acc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Ct[MM::crow(r, lane) * LDD + fm] = acc[r];
-}
+// Where the B operand of rank64_tiles keeps element (n, k): BRows: n * LDD + k (16 rows of K contiguous values, as A);
+// BCols: k * LDD + n (K-major, a 64 x 16 block of a matrix stored K x N).
+struct BRows { static constexpr int N = LDD, K = 1; };
+struct BCols { static constexpr int N = 1, K = LDD; };
 
-// NT such tiles, tile t at Ct + t * cstride with A rows at Ar + t * astride and B rows at Br + t * bstride (a stride of 0 shares
-// the operand; the repeated reads of a shared operand are to the same LDS words).  A tile is a chain of 16 DEPENDENT
+// C(16 x 16 tile at Ct) -= A(16 rows at Ar) B^T over K = 64, everything in LDS with leading dimension LDD, for NT tiles: tile t
+// at Ct + t * cstride with A rows at Ar + t * astride and B at Br + t * bstride in layout BL (a stride of 0 shares the operand:
+// a shared A is read once, the repeated reads of a shared B are to the same LDS words).  A tile is a chain of 16 DEPENDENT
 // MFMAs (one accumulator): alone it runs at the MFMA's latency, 1150 cycles (float32) for 512 cycles of matrix-core work, and
 // these tiles were the longest item of every panel phase (tools/probes/potrf_stamps.py).  Here the NT chains advance together,
-// so their MFMAs overlap; each tile's own arithmetic and its order are those of rank64_tile (bit-identical).
-template <typename T, int NT>
+// so their MFMAs overlap; each tile keeps the arithmetic and the order of a lone chain over k = 0 .. 63 (bit-identical).
+template <typename T, int NT, typename BL = BRows>
 __device__ __forceinline__ void rank64_tiles(T* Ct, int cstride, const T* Ar, int astride, const T* Br, int bstride, int lane) {
     typedef Mma16<T> MM;
     const int fm = lane & 15, fk = lane >> 4;
@@ -486,8 +313,8 @@ __device__ __forceinline__ void rank64_tiles(T* Ct, int cstride, const T* Ar, in
         for (int kk = 4 * g; kk < 4 * g + 4; ++kk) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                av[t][kk] = Ar[t * astride + fm * LDD + 4 * kk + fk];
-                bv[t][kk] = Br[t * bstride + fm * LDD + 4 * kk + fk];
+                av[t][kk] = (t > 0 && astride == 0) ? av[0][kk] : Ar[t * astride + fm * LDD + 4 * kk + fk];
+                bv[t][kk] = Br[t * bstride + fm * BL::N + (4 * kk + fk) * BL::K];
             }
         }
     };
@@ -513,7 +340,7 @@ __device__ __forceinline__ void rank64_tiles(T* Ct, int cstride, const T* Ar, in
 }
 
 // ONE tile with its K range cut into four accumulator chains (k = 4 kk + fk, chain kk mod 4), summed at the end: for the tile
-// every wave updates alone before the first sub-panel can start (U0).  Not the summation order of rank64_tile -- the panel and
+// every wave updates alone before the first sub-panel can start (U0).  Not the summation order of rank64_tiles -- the panel and
 // the inverse's row-block workgroups both take this route for the same data, so they still agree bit for bit.
 template <typename T>
 __device__ __forceinline__ void rank64_tile_split(T* Ct, const T* Ar, const T* Br, int lane) {
@@ -535,38 +362,58 @@ __device__ __forceinline__ void rank64_tile_split(T* Ct, const T* Ar, const T* B
     for (int r = 0; r < 4; ++r) Ct[MM::crow(r, lane) * LDD + fm] = -((acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]));
 }
 
-// One column block CB of the blocked substitution  X L11^T = A21  for NS 16-row strips of the slab (strip s at Xw + s * sstride),
-// by ONE wave:  X_cb = (A_cb - sum_{kb < cb} X_kb L[cb][kb]^T) Dinv_cb^T.  The strips' accumulator chains advance together
-// (see rank64_tiles); per strip the arithmetic and its order do not depend on NS.
-template <typename T, int CB, int NS = 1>
-__device__ __forceinline__ void slab_subst_step(T* Xw, const T* S, const T* Dinv, int lane, int sstride = 0) {
+// The two blocked substitutions against the factored diagonal block, as layouts of one step.  A strip is 16 vectors of 64
+// unknowns; element k of vector i sits at at(i, k), and out(row, col, k0) places element (row, col) of an MFMA result whose
+// block of unknowns starts at k0.
+//   RowStrips  X L11^T = A21 on the slab: a strip is 16 ROWS, the unknowns run along a row; L is the MFMA's B operand.
+//   ColStrips  L11 Y = R on a chunk of W's row block: a strip is 16 COLUMNS, the unknowns run down a column; L is the A operand.
+struct RowStrips {
+    static __device__ __forceinline__ int at(int i, int k) { return i * LDD + k; }
+    static __device__ __forceinline__ int out(int row, int col, int k0) { return at(row, k0 + col); }
+    template <typename T> static __device__ __forceinline__ typename Mma16<T>::acc_t mma(T x, T l, typename Mma16<T>::acc_t c) {
+        return Mma16<T>::mma(x, l, c);
+    }
+};
+struct ColStrips {
+    static __device__ __forceinline__ int at(int i, int k) { return k * LDD + i; }
+    static __device__ __forceinline__ int out(int row, int col, int k0) { return at(col, k0 + row); }
+    template <typename T> static __device__ __forceinline__ typename Mma16<T>::acc_t mma(T x, T l, typename Mma16<T>::acc_t c) {
+        return Mma16<T>::mma(l, x, c);
+    }
+};
+
+// Block B of the unknowns for NS strips (strip s at X + s * stride; the solution overwrites the right-hand side), by ONE wave:
+//   RowStrips  X_b = (A_b - sum_{kb < b} X_kb L[b][kb]^T) Dinv_b^T          ColStrips  Y_b = Dinv_b (R_b - sum_{kb < b} L[b][kb] Y_kb)
+// The strips' accumulator chains advance together (see rank64_tiles); per strip the arithmetic and its order do not depend on NS.
+template <typename T, typename LY, int B, int NS = 1>
+__device__ __forceinline__ void subst_step(T* X, const T* S, const T* Dinv, int lane, int stride = 0) {
     typedef Mma16<T> MM;
     const int fm = lane & 15, fk = lane >> 4;
     typename MM::acc_t acc[NS];
-    constexpr int KS = CB * 4 > 0 ? CB * 4 : 1;
+    constexpr int KS = B * 4 > 0 ? B * 4 : 1;
     T lv[KS], xv[NS][KS], dv[4];
 #pragma unroll
-    for (int q = 0; q < CB * 4; ++q) lv[q] = S[(CB * SB + fm) * LDD + 4 * q + fk];       // k = 16 kb + 4 kk + fk = 4 q + fk
+    for (int q = 0; q < B * 4; ++q) lv[q] = S[(B * SB + fm) * LDD + 4 * q + fk];          // k = 16 kb + 4 kk + fk = 4 q + fk
 #pragma unroll
     for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int q = 0; q < CB * 4; ++q) xv[s][q] = Xw[s * sstride + fm * LDD + 4 * q + fk];
+        for (int q = 0; q < B * 4; ++q) xv[s][q] = X[s * stride + LY::at(fm, 4 * q + fk)];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) dv[kk] = Dinv[(CB * SB + fm) * LDI + 4 * kk + fk];
+    for (int kk = 0; kk < 4; ++kk) dv[kk] = Dinv[(B * SB + fm) * LDI + 4 * kk + fk];
 #pragma unroll
     for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[s][r] = -Xw[s * sstride + MM::crow(r, lane) * LDD + CB * SB + fm];
+        for (int r = 0; r < 4; ++r) acc[s][r] = -X[s * stride + LY::out(MM::crow(r, lane), fm, B * SB)];
     if constexpr (sizeof(T) == 4) __builtin_amdgcn_sched_barrier(0);   // float64: MFMA-bound, the compiler's own interleaving is better
 #pragma unroll
-    for (int q = 0; q < CB * 4; ++q)
+    for (int q = 0; q < B * 4; ++q)
 #pragma unroll
-        for (int s = 0; s < NS; ++s) acc[s] = MM::mma(xv[s][q], lv[q], acc[s]);
+        for (int s = 0; s < NS; ++s) acc[s] = LY::template mma<T>(xv[s][q], lv[q], acc[s]);
     wave_sync();
 #pragma unroll
     for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Xw[s * sstride + MM::crow(r, lane) * LDD + CB * SB + fm] = -acc[s][r];
+        for (int r = 0; r < 4; ++r) X[s * stride + LY::out(MM::crow(r, lane), fm, B * SB)] = -acc[s][r];
     wave_sync();
     typename MM::acc_t y[NS];
     T xr[NS][4];
@@ -574,24 +421,24 @@ __device__ __forceinline__ void slab_subst_step(T* Xw, const T* S, const T* Dinv
     for (int s = 0; s < NS; ++s) {
         y[s] = typename MM::acc_t{T(0), T(0), T(0), T(0)};
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) xr[s][kk] = Xw[s * sstride + fm * LDD + CB * SB + 4 * kk + fk];
+        for (int kk = 0; kk < 4; ++kk) xr[s][kk] = X[s * stride + LY::at(fm, B * SB + 4 * kk + fk)];
     }
     if constexpr (sizeof(T) == 4) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
-        for (int s = 0; s < NS; ++s) y[s] = MM::mma(xr[s][kk], dv[kk], y[s]);
+        for (int s = 0; s < NS; ++s) y[s] = LY::template mma<T>(xr[s][kk], dv[kk], y[s]);
     wave_sync();
 #pragma unroll
     for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Xw[s * sstride + MM::crow(r, lane) * LDD + CB * SB + fm] = y[s][r];
+        for (int r = 0; r < 4; ++r) X[s * stride + LY::out(MM::crow(r, lane), fm, B * SB)] = y[s][r];
     wave_sync();
 }
 
 // F0 work of waves 1..3 on the diagonal block: S -= P P^T on the tiles ON OR BELOW the diagonal of column tiles 1..3 (the
 // factorisation never reads above it; six of the twelve tiles used to be updated for nothing) -- wave 1: (1..3, 1), wave 2:
-// (2..3, 2), wave 3: (3, 3).  panel_body2 and prow_body both come through here: same arithmetic on the same data.
+// (2..3, 2), wave 3: (3, 3).  panel_body and prow_body both come through here: same arithmetic on the same data.
 template <typename T>
 __device__ __forceinline__ void diag_prev_update(T* S, const T* Ps, int w, int lane) {
     constexpr int RS = SB * LDD;
@@ -600,34 +447,38 @@ __device__ __forceinline__ void diag_prev_update(T* S, const T* Ps, int w, int l
     else if (w == 3) rank64_tile_split<T>(S + 3 * RS + 3 * SB, Ps + 3 * RS, Ps + 3 * RS, lane);
 }
 
-// Panel with the idle waves put to work.  While wave 0 factors a 16-column sub-panel in registers (2.7 us, 4 times per
-// panel) the other three waves used to wait at the barrier; here they run everything that does not depend on the
-// sub-panel being factored:
+// FULL 64-wide panel.  grid.x = nslab workgroups of 4 waves, each factors the
+// diagonal block in LDS (redundantly: no grid-wide dependency) -- 4 sub-panels of 16 columns, each factored
+// by wave 0 in registers, the rest of the block updated by all waves with 16x16x4 MFMAs -- invert the four
+// 16x16 diagonal sub-blocks, and solve their own 64-row slab  L21 = A21 L11^-T  by blocked substitution
+// (MFMA updates, multiplication by the 16x16 inverses).  The slab's global loads are issued before the
+// factorisation so their latency is hidden.  Block 0 publishes L11 to the side buffer (other workgroups
+// still read A11); potrf_finalize_kernel copies the factors into place at the end.
+// `pre`: the rank-64 update of the PREVIOUS panel (columns [j0-64, j0)) has not been applied to this block column
+// yet; the workgroup applies it to its own diagonal block and slab first (two 64x64x64 MFMA products on blocks
+// that are loaded together with everything else), so that the previous panel's update of the REST of the
+// trailing matrix can run concurrently in the same launch (potrf_step_kernel).
+// The idle waves are put to work: while wave 0 factors a 16-column sub-panel in registers (2.7 us, 4 times per panel) the
+// other three waves run everything that does not depend on the sub-panel being factored:
 //   F0: the previous panel's rank-64 update of columns 16..63 of the diagonal block (columns 0..15, which sub-panel 0
 //       needs, are updated by all waves first);
 //   F1: that update on the slab (X -= Q P^T), wave 1 also inverts diagonal sub-block 0;
 //   F2, F3: column blocks 0 and 1 of the slab substitution (wave 1 inverts sub-blocks 1, 2);
 // so that after the last sub-panel only sub-block 3's inverse, column blocks 2 and 3 of the substitution and the store
-// remain (5.5 -> ~2 us) -- same arithmetic in the same order per element as panel_body, bit-identical results.
-// Work on a slab strip is wave-local (wave_sync); every phase ends in ONE barrier that all four waves reach.
+// remain (5.5 -> ~2 us; 26.6 -> 23.4 us per launch against factoring first and solving after, with the same arithmetic in the
+// same order per element).  Work on a slab strip is wave-local (wave_sync); every phase ends in ONE barrier that all four
+// waves reach.
 template <typename T>
-__device__ __forceinline__ void panel_body2(unsigned char* panel_smem, T* __restrict__ A, int64_t n, int64_t lda,
-                                            int64_t sA, int64_t j0, T* __restrict__ wsL, int64_t npanels,
-                                            int32_t* __restrict__ info, int64_t blk, int64_t b, bool pre) {
-    typedef Mma16<T> MM;
-    typedef typename MM::acc_t acc_t;
-    T* S = reinterpret_cast<T*>(panel_smem);            // [64][LDD]   diagonal block -> L11
-    T* Xs = S + NB * LDD;                               // [64][LDD]   this workgroup's slab
-    T* Dinv = Xs + NB * LDD;                            // [4][16][LDI] inverses of the 16x16 diagonal sub-blocks
-    T* rd = Dinv + 4 * SB * LDI;                        // [64] reciprocal pivots
-    T* Ps = rd + NB;                                    // [64][LDD]   previous panel's L, diagonal-block rows
-    T* Qs = Ps + NB * LDD;                              // [64][LDD]   previous panel's L, slab rows
+__device__ __forceinline__ void panel_body(unsigned char* panel_smem, T* __restrict__ A, int64_t n, int64_t lda,
+                                           int64_t sA, int64_t j0, T* __restrict__ wsL, int64_t npanels,
+                                           int32_t* __restrict__ info, int64_t blk, int64_t b, bool pre) {
+    const PanelLds<T> lds(panel_smem);
+    T *const S = lds.S, *const Xs = lds.Xs, *const Dinv = lds.Dinv, *const rd = lds.rd, *const Ps = lds.Ps, *const Qs = lds.Qs;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     T* Ab = A + b * sA;
     const int64_t pj = j0 / NB;
     const int64_t r0 = j0 + NB + blk * NB;
     const int rows = r0 >= n ? 0 : (int)((n - r0) < NB ? (n - r0) : NB);
-    const int fm = lane & 15, fk = lane >> 4;
 #ifdef NSGP_POTRF_STAMPS
     unsigned long long pst[16] = {}, wst[8] = {};
     const bool pst_on = tid == 0 && blk == 0 && b == 0;
@@ -677,7 +528,7 @@ __device__ __forceinline__ void panel_body2(unsigned char* panel_smem, T* __rest
     const bool slab = rows > 0;
     int bad = 0;
     // ---- F0 ----
-    if (w == 0) { const int bd = factor_subpanel<T, 0>(S, rd, Qs + NB * LDD, lane); if (bad == 0) bad = bd; NSGP_PSTAMP(3); }
+    if (w == 0) { const int bd = factor_subpanel<T, 0>(S, rd, lds.cb, lane); if (bad == 0) bad = bd; NSGP_PSTAMP(3); }
     else if (pre) {
         diag_prev_update<T>(S, Ps, w, lane);
         // ... and, behind the short lists, slab tiles that wait for nothing: X -= Q P^T, (strip, column tile) = (0, 2), (1, 2)
@@ -685,33 +536,13 @@ __device__ __forceinline__ void panel_body2(unsigned char* panel_smem, T* __rest
     }
     NSGP_WSTAMP(0);
     __syncthreads();
-#define NSGP_TRAIL(C0)                                                                                \
-    {                                                                                                 \
-        constexpr int B0 = C0 / SB;                                                                   \
-        constexpr int NT = (3 - B0) * (4 - B0) / 2;      /* lower tiles of the trailing block */      \
-        for (int q = w; q < NT; q += 4) {                                                             \
-            int ti = B0 + 1, tj = B0 + 1, c = q;                                                      \
-            while (c > ti - (B0 + 1)) { c -= ti - B0; ++ti; }                                         \
-            tj = B0 + 1 + c;                                                                          \
-            acc_t acc;                                                                                \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r)                                             \
-                acc[r] = S[(ti * SB + MM::crow(r, lane)) * LDD + tj * SB + fm];                       \
-            _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) {                                        \
-                const T av = -S[(ti * SB + fm) * LDD + C0 + 4 * kk + fk];                             \
-                const T bv = S[(tj * SB + fm) * LDD + C0 + 4 * kk + fk];                              \
-                acc = MM::mma(av, bv, acc);                                                           \
-            }                                                                                         \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r)                                             \
-                S[(ti * SB + MM::crow(r, lane)) * LDD + tj * SB + fm] = acc[r];                       \
-        }                                                                                             \
-        NSGP_WSTAMP(1 + 2 * B0);                                                                      \
-        if (NT > 0) __syncthreads();                                                                  \
-    }
     NSGP_PSTAMP(4);
-    NSGP_TRAIL(0)
+    diag_trail_update<T, 0>(S, w, lane);
+    NSGP_WSTAMP(1);
+    __syncthreads();
     NSGP_PSTAMP(5);
     // ---- F1 ----
-    if (w == 0) { const int bd = factor_subpanel<T, 16>(S, rd, Qs + NB * LDD, lane); if (bad == 0) bad = bd; NSGP_PSTAMP(6); }
+    if (w == 0) { const int bd = factor_subpanel<T, 16>(S, rd, lds.cb, lane); if (bad == 0) bad = bd; NSGP_PSTAMP(6); }
     else {
         // X -= Q P^T, 16 (strip, column tile) tasks over F0 .. F2, at most three to a wave and phase (float64: a tile is 1024
         // cycles of matrix-core time, a sub-panel factorisation 4900): column tiles 0 and 1 now (the substitution needs them
@@ -726,10 +557,12 @@ __device__ __forceinline__ void panel_body2(unsigned char* panel_smem, T* __rest
     NSGP_WSTAMP(2);
     __syncthreads();
     NSGP_PSTAMP(7);
-    NSGP_TRAIL(16)
+    diag_trail_update<T, 16>(S, w, lane);
+    NSGP_WSTAMP(3);
+    __syncthreads();
     NSGP_PSTAMP(8);
     // ---- F2 ----
-    if (w == 0) { const int bd = factor_subpanel<T, 32>(S, rd, Qs + NB * LDD, lane); if (bad == 0) bad = bd; NSGP_PSTAMP(9); }
+    if (w == 0) { const int bd = factor_subpanel<T, 32>(S, rd, lds.cb, lane); if (bad == 0) bad = bd; NSGP_PSTAMP(9); }
     else {
         if (w == 1) {
             invert_subblock<T>(S, rd, Dinv, 1, lane);
@@ -738,28 +571,29 @@ __device__ __forceinline__ void panel_body2(unsigned char* panel_smem, T* __rest
         } else if (slab) {                               // waves 2, 3: strips {0, 2} and {1, 3}
             if (pre) rank64_tiles<T, 2>(Xs + ((w - 2) * SB) * LDD + 3 * SB, 2 * SB * LDD, Qs + ((w - 2) * SB) * LDD, 2 * SB * LDD,
                                         Ps + (3 * SB) * LDD, 0, lane);
-            slab_subst_step<T, 0, 2>(Xs + ((w - 2) * SB) * LDD, S, Dinv, lane, 2 * SB * LDD);
+            subst_step<T, RowStrips, 0, 2>(Xs + ((w - 2) * SB) * LDD, S, Dinv, lane, 2 * SB * LDD);
         }
     }
     NSGP_WSTAMP(4);
     __syncthreads();
     NSGP_PSTAMP(10);
-    NSGP_TRAIL(32)
+    diag_trail_update<T, 32>(S, w, lane);
+    NSGP_WSTAMP(5);
+    __syncthreads();
     NSGP_PSTAMP(11);
     // ---- F3 ----
-    if (w == 0) { const int bd = factor_subpanel<T, 48>(S, rd, Qs + NB * LDD, lane); if (bad == 0) bad = bd; NSGP_PSTAMP(12); }
+    if (w == 0) { const int bd = factor_subpanel<T, 48>(S, rd, lds.cb, lane); if (bad == 0) bad = bd; NSGP_PSTAMP(12); }
     else if (w == 1) invert_subblock<T>(S, rd, Dinv, 2, lane);
     else if (slab) {
-        slab_subst_step<T, 1, 2>(Xs + ((w - 2) * SB) * LDD, S, Dinv, lane, 2 * SB * LDD);
+        subst_step<T, RowStrips, 1, 2>(Xs + ((w - 2) * SB) * LDD, S, Dinv, lane, 2 * SB * LDD);
     }
     NSGP_WSTAMP(6);
     __syncthreads();
     NSGP_PSTAMP(13);
-#undef NSGP_TRAIL
     // ---- after the last sub-panel ----
     if (w == 1) invert_subblock<T>(S, rd, Dinv, 3, lane);
     else if (w >= 2 && slab) {
-        slab_subst_step<T, 2, 2>(Xs + ((w - 2) * SB) * LDD, S, Dinv, lane, 2 * SB * LDD);
+        subst_step<T, RowStrips, 2, 2>(Xs + ((w - 2) * SB) * LDD, S, Dinv, lane, 2 * SB * LDD);
     }
     if (blk == 0) {
         T* dst = wsL + (b * npanels + pj) * NB * NB;
@@ -776,7 +610,7 @@ __device__ __forceinline__ void panel_body2(unsigned char* panel_smem, T* __rest
     NSGP_PSTAMP(14);
     if (slab) {                                          // workgroup-uniform
         T* Xw = Xs + (w * SB) * LDD;                     // last column block: every wave its own strip
-        slab_subst_step<T, 3>(Xw, S, Dinv, lane);
+        subst_step<T, RowStrips, 3>(Xw, S, Dinv, lane);
 #pragma unroll
         for (int i = 0; i < SB; ++i)
             if (w * SB + i < rows) Ab[(r0 + w * SB + i) * lda + j0 + lane] = Xw[i * LDD + lane];
@@ -885,9 +719,7 @@ __global__ __launch_bounds__(256) void potrf_step_kernel(T* __restrict__ A, int6
     const int64_t lin = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;     // matrix fastest: see potrf_inv_step_kernel
     const int64_t blk = lin / gridDim.y, b = lin % gridDim.y;
     if (blk < nslab) {
-        // bit 1 of `pre`: the round-1 panel (NSGP_POTRF_PANEL=1), kept for A/B timing
-        if (pre & 2) panel_body<T>(panel_smem, A, n, lda, sA, j0, wsL, npanels, info, blk, b, (pre & 1) != 0);
-        else panel_body2<T>(panel_smem, A, n, lda, sA, j0, wsL, npanels, info, blk, b, (pre & 1) != 0);
+        panel_body<T>(panel_smem, A, n, lda, sA, j0, wsL, npanels, info, blk, b, pre != 0);
     }
     else syrk_body<T>(panel_smem, A, n, lda, sA, j0 - NB, j0 + NB, wcols, blk - nslab, b);
 }
@@ -901,126 +733,16 @@ __global__ __launch_bounds__(256) void potrf_step_kernel(T* __restrict__ A, int6
 // the factor -- on CUs those launches leave idle.  The eight latency-bound launches of the recursive inverse (trtri: 162 us
 // for 3 x 1024^2) disappear from the DSVI whitening chain.
 
-// C(16 x 16 tile at Ct) -= A(16 rows at Ar, K contiguous) B(64 x 16 at Bk, K-major: B(k, n) = Bk[k * LDD + n])
-template <typename T>
-__device__ __forceinline__ void rank64_tile_kn(T* Ct, const T* Ar, const T* Bk, int lane) {
-    typedef Mma16<T> MM;
-    const int fm = lane & 15, fk = lane >> 4;
-    typename MM::acc_t acc;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = Ct[MM::crow(r, lane) * LDD + fm];
-#pragma unroll
-    for (int kk = 0; kk < NB / 4; ++kk) acc = MM::mma(-Ar[fm * LDD + 4 * kk + fk], Bk[(4 * kk + fk) * LDD + fm], acc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Ct[MM::crow(r, lane) * LDD + fm] = acc[r];
-}
-
-// NT such tiles that share A: tile t at Ct + 16 t against B columns Bk + 16 t (accumulator chains interleaved, see rank64_tiles)
-template <typename T, int NT>
-__device__ __forceinline__ void rank64_tiles_kn(T* Ct, const T* Ar, const T* Bk, int lane) {
-    typedef Mma16<T> MM;
-    const int fm = lane & 15, fk = lane >> 4;
-    typename MM::acc_t acc[NT];
-    T av[NB / 4], bv[NT][NB / 4];
-    auto fetch = [&](int g) __attribute__((always_inline)) {       // as rank64_tiles: one group of k-steps ahead
-#pragma unroll
-        for (int kk = 4 * g; kk < 4 * g + 4; ++kk) {
-            av[kk] = Ar[fm * LDD + 4 * kk + fk];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) bv[t][kk] = Bk[t * SB + (4 * kk + fk) * LDD + fm];
-        }
-    };
-    fetch(0);
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[t][r] = -Ct[t * SB + MM::crow(r, lane) * LDD + fm];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if (g < 3) fetch(g + 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int kk = 4 * g; kk < 4 * g + 4; ++kk)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = MM::mma(av[kk], bv[t][kk], acc[t]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Ct[t * SB + MM::crow(r, lane) * LDD + fm] = -acc[t][r];
-}
-
-// Row block RB of the blocked substitution  L11 Y = R  for NS 16-COLUMN strips of a 64 x 64 block (strip s at Rc + s * cstride),
-// by ONE wave:  Y_rb = Dinv_rb (R_rb - sum_{kb < rb} L[rb][kb] Y_kb)      (Y overwrites R; Rc points at the first strip's first
-// column).  The strips' accumulator chains advance together; per strip the arithmetic and its order do not depend on NS.
-template <typename T, int RB, int NS = 1>
-__device__ __forceinline__ void prow_subst_step(T* Rc, const T* S, const T* Dinv, int lane, int cstride = 0) {
-    typedef Mma16<T> MM;
-    const int fm = lane & 15, fk = lane >> 4;
-    typename MM::acc_t acc[NS];
-    constexpr int KS = RB * 4 > 0 ? RB * 4 : 1;
-    T lv[KS], rv[NS][KS], dv[4];
-#pragma unroll
-    for (int q = 0; q < RB * 4; ++q) lv[q] = S[(RB * SB + fm) * LDD + 4 * q + fk];       // k = 16 kb + 4 kk + fk = 4 q + fk
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int q = 0; q < RB * 4; ++q) rv[s][q] = Rc[s * cstride + (4 * q + fk) * LDD + fm];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) dv[kk] = Dinv[(RB * SB + fm) * LDI + 4 * kk + fk];
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[s][r] = -Rc[s * cstride + (RB * SB + MM::crow(r, lane)) * LDD + fm];
-    if constexpr (sizeof(T) == 4) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < RB * 4; ++q)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) acc[s] = MM::mma(lv[q], rv[s][q], acc[s]);
-    wave_sync();
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Rc[s * cstride + (RB * SB + MM::crow(r, lane)) * LDD + fm] = -acc[s][r];
-    wave_sync();
-    typename MM::acc_t y[NS];
-    T rr[NS][4];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        y[s] = typename MM::acc_t{T(0), T(0), T(0), T(0)};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) rr[s][kk] = Rc[s * cstride + (RB * SB + 4 * kk + fk) * LDD + fm];
-    }
-    if constexpr (sizeof(T) == 4) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) y[s] = MM::mma(dv[kk], rr[s][kk], y[s]);
-    wave_sync();
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Rc[s * cstride + (RB * SB + MM::crow(r, lane)) * LDD + fm] = y[s][r];
-    wave_sync();
-}
-
 // Row block j of the inverse, 64-column chunk c (c0 = 64 c <= j0):  W[j][c] <- L_jj^-1 (W[j][c] - L[j][j-1] W[j-1][c]).
-// Same phases as panel_body2 (the diagonal block is factored redundantly; the idle waves do the chunk's work).
+// Same phases as panel_body (the diagonal block is factored redundantly; the idle waves do the chunk's work).
 template <typename T>
 __device__ __forceinline__ void prow_body(unsigned char* panel_smem, const T* __restrict__ A, int64_t n, int64_t lda,
                                           int64_t sA, int64_t j0, T* __restrict__ X, int64_t ldx, int64_t sX, int64_t c,
                                           int64_t b, bool pre, float* __restrict__ X32) {
     // X32 != null (float64 chain of a float32 model): a float32 copy of W (same leading dimension / batch stride in
     // elements) is written along with it -- the cast pass the layers would otherwise launch
-    typedef Mma16<T> MM;
-    typedef typename MM::acc_t acc_t;
-    T* S = reinterpret_cast<T*>(panel_smem);            // [64][LDD]   diagonal block -> L11
-    T* Rs = S + NB * LDD;                               // [64][LDD]   the chunk of W's row block
-    T* Dinv = Rs + NB * LDD;                            // [4][16][LDI]
-    T* rd = Dinv + 4 * SB * LDI;                        // [64]
-    T* Ps = rd + NB;                                    // [64][LDD]   L[j][j-1]
-    T* Qs = Ps + NB * LDD;                              // [64][LDD]   W[j-1][c]   (K x N)
+    const PanelLds<T> lds(panel_smem);                  // Xs: the chunk of W's row block; Ps: L[j][j-1]; Qs: W[j-1][c] (K x N)
+    T *const S = lds.S, *const Rs = lds.Xs, *const Dinv = lds.Dinv, *const rd = lds.rd, *const Ps = lds.Ps, *const Qs = lds.Qs;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const T* Ab = A + b * sA;
     T* Xb = X + b * sX;
@@ -1028,7 +750,6 @@ __device__ __forceinline__ void prow_body(unsigned char* panel_smem, const T* __
     const bool diag = c0 == j0;                          // the chunk that starts as the identity
     const bool upd = pre && !diag;                       // chunks left of the diagonal carry the previous panel's update
     const bool first = c0 + NB == j0;                    // chunk j - 1: no earlier update has written it
-    const int fm = lane & 15, fk = lane >> 4;
     if (diag) {                                          // zero the rest of these rows (W is lower triangular); off the
         for (int i = w; i < NB; i += 4)                  // critical path: this workgroup has no chunk to load
             for (int64_t cc = j0 + NB + lane; cc < n; cc += 64) {
@@ -1076,73 +797,54 @@ __device__ __forceinline__ void prow_body(unsigned char* panel_smem, const T* __
         __syncthreads();
     }
     // ---- F0 ----
-    if (w == 0) (void)factor_subpanel<T, 0>(S, rd, Qs + NB * LDD, lane);
+    if (w == 0) (void)factor_subpanel<T, 0>(S, rd, lds.cb, lane);
     else if (pre) {
         diag_prev_update<T>(S, Ps, w, lane);
     }
     __syncthreads();
-#define NSGP_TRAIL(C0)                                                                                \
-    {                                                                                                 \
-        constexpr int B0 = C0 / SB;                                                                   \
-        constexpr int NT = (3 - B0) * (4 - B0) / 2;                                                   \
-        for (int q = w; q < NT; q += 4) {                                                             \
-            int ti = B0 + 1, tj = B0 + 1, cq = q;                                                     \
-            while (cq > ti - (B0 + 1)) { cq -= ti - B0; ++ti; }                                       \
-            tj = B0 + 1 + cq;                                                                         \
-            acc_t acc;                                                                                \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r)                                             \
-                acc[r] = S[(ti * SB + MM::crow(r, lane)) * LDD + tj * SB + fm];                       \
-            _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) {                                        \
-                const T av = -S[(ti * SB + fm) * LDD + C0 + 4 * kk + fk];                             \
-                const T bv = S[(tj * SB + fm) * LDD + C0 + 4 * kk + fk];                              \
-                acc = MM::mma(av, bv, acc);                                                           \
-            }                                                                                         \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r)                                             \
-                S[(ti * SB + MM::crow(r, lane)) * LDD + tj * SB + fm] = acc[r];                       \
-        }                                                                                             \
-        if (NT > 0) __syncthreads();                                                                  \
-    }
-    NSGP_TRAIL(0)
+    diag_trail_update<T, 0>(S, w, lane);
+    __syncthreads();
     // R -= L[j][j-1] W[j-1][c]: tiles (row block rb, column tiles t, t + 1, ...) share the rows of L
     auto rtiles2 = [&](int rb, int t) __attribute__((always_inline)) {
-        rank64_tiles_kn<T, 2>(Rs + (rb * SB) * LDD + t * SB, Ps + (rb * SB) * LDD, Qs + t * SB, lane);
+        rank64_tiles<T, 2, BCols>(Rs + (rb * SB) * LDD + t * SB, SB, Ps + (rb * SB) * LDD, 0, Qs + t * SB, SB, lane);
     };
     // ---- F1 ----  (the substitution walks row blocks 0, 1, 2, 3 of EVERY column strip: all column tiles of row blocks 0
     // and 1 first)
-    if (w == 0) (void)factor_subpanel<T, 16>(S, rd, Qs + NB * LDD, lane);
+    if (w == 0) (void)factor_subpanel<T, 16>(S, rd, lds.cb, lane);
     else if (w == 1) {
         invert_subblock<T>(S, rd, Dinv, 0, lane);
         if (upd) rtiles2(2, 0);
     } else if (upd) {
-        rank64_tiles_kn<T, 4>(Rs + ((w - 2) * SB) * LDD, Ps + ((w - 2) * SB) * LDD, Qs, lane);
+        rank64_tiles<T, 4, BCols>(Rs + ((w - 2) * SB) * LDD, SB, Ps + ((w - 2) * SB) * LDD, 0, Qs, SB, lane);
     }
     __syncthreads();
-    NSGP_TRAIL(16)
+    diag_trail_update<T, 16>(S, w, lane);
+    __syncthreads();
     // ---- F2 ----
-    if (w == 0) (void)factor_subpanel<T, 32>(S, rd, Qs + NB * LDD, lane);
+    if (w == 0) (void)factor_subpanel<T, 32>(S, rd, lds.cb, lane);
     else if (w == 1) {
         invert_subblock<T>(S, rd, Dinv, 1, lane);
         if (upd) rtiles2(2, 2);
     } else {
         if (upd) rtiles2(3, 2 * (w - 2));
-        prow_subst_step<T, 0, 2>(Rs + (w - 2) * SB, S, Dinv, lane, 2 * SB);          // column strips {0, 2} and {1, 3}
+        subst_step<T, ColStrips, 0, 2>(Rs + (w - 2) * SB, S, Dinv, lane, 2 * SB);          // column strips {0, 2} and {1, 3}
     }
     __syncthreads();
-    NSGP_TRAIL(32)
+    diag_trail_update<T, 32>(S, w, lane);
+    __syncthreads();
     // ---- F3 ----
-    if (w == 0) (void)factor_subpanel<T, 48>(S, rd, Qs + NB * LDD, lane);
+    if (w == 0) (void)factor_subpanel<T, 48>(S, rd, lds.cb, lane);
     else if (w == 1) invert_subblock<T>(S, rd, Dinv, 2, lane);
     else {
-        prow_subst_step<T, 1, 2>(Rs + (w - 2) * SB, S, Dinv, lane, 2 * SB);
+        subst_step<T, ColStrips, 1, 2>(Rs + (w - 2) * SB, S, Dinv, lane, 2 * SB);
     }
     __syncthreads();
-#undef NSGP_TRAIL
     if (w == 1) invert_subblock<T>(S, rd, Dinv, 3, lane);
     else if (w >= 2) {
-        prow_subst_step<T, 2, 2>(Rs + (w - 2) * SB, S, Dinv, lane, 2 * SB);
+        subst_step<T, ColStrips, 2, 2>(Rs + (w - 2) * SB, S, Dinv, lane, 2 * SB);
     }
     __syncthreads();
-    prow_subst_step<T, 3>(Rs + w * SB, S, Dinv, lane);                    // last row block: every wave its column strip
+    subst_step<T, ColStrips, 3>(Rs + w * SB, S, Dinv, lane);                    // last row block: every wave its column strip
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < SB; ++i) {
@@ -1218,7 +920,7 @@ __global__ __launch_bounds__(256) void potrf_inv_step_kernel(T* __restrict__ A, 
     const int64_t lin = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
     int64_t blk = lin / gridDim.y;
     const int64_t b = lin % gridDim.y;
-    if (blk < nslab) { panel_body2<T>(panel_smem, A, n, lda, sA, j0, wsL, npanels, info, blk, b, pre != 0); return; }
+    if (blk < nslab) { panel_body<T>(panel_smem, A, n, lda, sA, j0, wsL, npanels, info, blk, b, pre != 0); return; }
     blk -= nslab;
     if (blk < nprow) { prow_body<T>(panel_smem, A, n, lda, sA, j0, X, ldx, sX, blk, b, pre != 0, X32); return; }
     blk -= nprow;
@@ -1288,7 +990,7 @@ int potrf_impl(T* A, int64_t n, int64_t lda, int64_t sA, int64_t batch, int32_t*
     if (batch > 65535) return -5;
     T* wsL = (T*)ws;
     hipStream_t st = (hipStream_t)stream;
-    const size_t step_lds = (4 * (size_t)NB * LDD + 4 * SB * LDI + NB + 2 * SB) * sizeof(T);   // + the pivot-column exchange buffers
+    constexpr size_t step_lds = PanelLds<T>::bytes;
     nsgp_opt_in_lds((const void*)potrf_step_kernel<T>, step_lds);
     // Two-level blocking for large matrices: rank-64 updates stay inside an outer panel of NB2 columns (they are
     // HBM-bound: 8 flop/B in float64), the rest of the trailing matrix is updated once per outer panel with
@@ -1296,8 +998,6 @@ int potrf_impl(T* A, int64_t n, int64_t lda, int64_t sA, int64_t batch, int32_t*
     // Outer panel width (measured, float64, MI355X): n = 2048: 985 / 954 / 921 / 878 us at 256 / 512 / 1024 / one level;
     // n = 4096: 2316 / 2245 / 2166 / 2147 us at 256 / 512 / 1024 / 2048; n = 8192: 7.53 / 6.99 / 7.02 / 7.53 ms;
     // n = 16384: 37.7 / 35.8 / 35.9 ms at 256 / 512 / 1024.  NSGP_POTRF_NB2 (units of 64 columns) overrides for A/B runs.
-    const char* pve = getenv("NSGP_POTRF_PANEL");
-    const int old_panel = (pve && pve[0] == '1') ? 2 : 0;
     const char* nb2e = getenv("NSGP_POTRF_NB2");
     const int64_t nb2m = (nb2e && atoi(nb2e) > 0) ? atoi(nb2e) : (n <= 4096 ? 32 : 16);
     const int64_t NB2 = n > 2048 ? nb2m * NB : n;
@@ -1321,7 +1021,7 @@ int potrf_impl(T* A, int64_t n, int64_t lda, int64_t sA, int64_t batch, int32_t*
                 ntile = tn * (tn + 1) / 2 + (tm - tn) * tn;
             }
             hipLaunchKernelGGL((potrf_step_kernel<T>), dim3((unsigned)(nslab + ntile), (unsigned)batch), dim3(256),
-                               step_lds, st, A, n, lda, sA, j0, wsL, npanels, info, nslab, pre | old_panel, wcols);
+                               step_lds, st, A, n, lda, sA, j0, wsL, npanels, info, nslab, pre, wcols);
         }
         if (Jend < n) {
             const int64_t rest = n - Jend, kw = Jend - J0;
@@ -1502,7 +1202,7 @@ int potrf_inv_impl(T* A, int64_t n, int64_t lda, int64_t sA, int64_t batch, int3
     if (batch > 65535) return -5;
     T* wsL = (T*)ws;
     hipStream_t st = (hipStream_t)stream;
-    const size_t step_lds = (4 * (size_t)NB * LDD + 4 * SB * LDI + NB + 2 * SB) * sizeof(T);   // + the pivot-column exchange buffers
+    constexpr size_t step_lds = PanelLds<T>::bytes;
     nsgp_opt_in_lds((const void*)potrf_inv_step_kernel<T>, step_lds);
     for (int64_t j0 = 0; j0 < n; j0 += NB) {
         const int pre = j0 > 0;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where a panel launch of the blocked Cholesky spends its time: runs nsgp_potrf on the DIAGNOSTIC build of the library
 (csrc/potrf.hip compiled with -DNSGP_POTRF_STAMPS; workgroup 0 of matrix 0 records the shader clock at the phase boundaries
-of panel_body2) and prints the median cycles per phase over the panels of one factorisation.
+of panel_body) and prints the median cycles per phase over the panels of one factorisation.
 
     make -C nonstationary-precip_amd/csrc stamps
     python tools/probes/potrf_stamps.py [N] [float32|float64] [batch]      (batch > 1 also prints a per-panel table)
