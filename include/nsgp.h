@@ -39,6 +39,14 @@ const char* nsgp_build_arch(void);          /* "gfx950" */
  * out: device, 8 x workgroups uint64; sink: device float (never written); iters: a positive multiple of 16. */
 int nsgp_mfma_rate_probe(int kind, int64_t workgroups, int iters, uint64_t* out, float* sink, void* stream);
 
+/* Host-side query (no GPU is touched): the launch every *_build_bwd_* entry point below makes for a (batch, n1, n2) problem
+ * (batch = 1 for Gibbs and Paciorek-Schervish), computed by the code the launch and the *_bwd_workspace queries run.
+ * rows_per_wg: rows of G a backward workgroup owns, 64, or 16 when the 64-row grid would have fewer than 256 workgroups;
+ * nti = ceil(n1 / rows_per_wg) and ntj = ceil(n2 / 256): the grid is (ntj, nti, batch), and the second pass sums ntj
+ * partials per row item, nti per column item and nti * ntj per global value.  An empty problem gives 0, 0, 0 (nothing is
+ * launched).  Returns 0, or -(index of the bad argument). */
+int nsgp_pairwise_bwd_plan(int64_t batch, int64_t n1, int64_t n2, int* rows_per_wg, int64_t* nti, int64_t* ntj);
+
 /* ------------------------------------------------------------------------------------------
  * K1  Diagonal Gibbs kernel (Rasmussen & Williams eq. 4.32)
  *     K[i,j] = os * prod_d sqrt(2 l1[d,i] l2[d,j] / (l1[d,i]^2 + l2[d,j]^2))
@@ -56,7 +64,10 @@ int nsgp_gibbs_build_fwd_f64(const double* x1, const double* x2, const double* e
                              int64_t n1, int64_t n2, int D, const double* outputscale, const double* diag_add,
                              double* K, int64_t ldk, void* stream);
 /* backward: G = dLoss/dK (n1,n2).  Outputs (any may be NULL): g_ell1:(D,n1) g_ell2:(D,n2)
- * g_x1:(n1,D) g_x2:(n2,D) g_os:(1).  Deterministic two-pass reduction (no atomics). */
+ * g_x1:(n1,D) g_x2:(n2,D) g_os:(1).  Deterministic two-pass reduction (no atomics).
+ * g_ell1 == g_ell2 AND g_x1 == g_x2 (each pair one buffer or both NULL, not both pairs NULL, n1 == n2): the row- and
+ * column-side gradients are SUMMED into them -- the x1 = x2, ell1 = ell2 case.  One pair shared and the other not is
+ * the ordinary mode: the shared buffer then receives one side's gradient only (both sides write it; do not do that). */
 size_t nsgp_gibbs_build_bwd_workspace(int64_t n1, int64_t n2, int D, int elem_size);
 int nsgp_gibbs_build_bwd_f32(const float* x1, const float* x2, const float* ell1, const float* ell2,
                              int64_t n1, int64_t n2, int D, const float* outputscale,
@@ -134,7 +145,8 @@ int nsgp_ps2d_build_fwd_f32(const float* x1, const float* x2, const float* sig1,
                             int64_t n1, int64_t n2, float jitter, float* K, int64_t ldk, void* stream);
 int nsgp_ps2d_build_fwd_f64(const double* x1, const double* x2, const double* sig1, const double* sig2,
                             int64_t n1, int64_t n2, double jitter, double* K, int64_t ldk, void* stream);
-/* backward wrt the per-point matrices: g_sig1:(n1,4) g_sig2:(n2,4) (either may be NULL) */
+/* backward wrt the per-point matrices: g_sig1:(n1,4) g_sig2:(n2,4) (either may be NULL).
+ * g_sig1 == g_sig2 (one buffer, n1 == n2): the row- and column-side gradients are SUMMED into it, as in K2. */
 size_t nsgp_ps2d_build_bwd_workspace(int64_t n1, int64_t n2, int elem_size);
 int nsgp_ps2d_build_bwd_f32(const float* x1, const float* x2, const float* sig1, const float* sig2,
                             int64_t n1, int64_t n2, float jitter, const float* G, int64_t ldg,
@@ -200,7 +212,8 @@ int nsgp_gemm_f64(int64_t M, int64_t N, int64_t K, double alpha,
  *     PeriodicKernel semantics as recalled in SURVEY A.2/A.7 (distance of x/period, division by ls_per).
  *     ls_rbf == NULL drops the RBF factor (plain PeriodicKernel); os == NULL means 1.  x as in K2.
  *     backward: g_x1/g_x2 (batch,n,D) per batch (NULL to skip), g_ls_rbf (batch,D), g_ls_per, g_period,
- *     g_os (batch); workspace from nsgp_rbf_periodic_build_bwd_workspace.
+ *     g_os (batch), any may be NULL; workspace from nsgp_rbf_periodic_build_bwd_workspace.
+ *     g_x1 == g_x2 (one buffer, n1 == n2): the row- and column-side gradients are SUMMED into it, as in K2.
  * ------------------------------------------------------------------------------------------ */
 int nsgp_rbf_periodic_build_fwd_f32(const float* x1, const float* x2, const float* ls_rbf, const float* ls_per,
                                     const float* period, const float* os, int64_t batch, int64_t n1, int64_t n2, int D,

@@ -454,6 +454,13 @@ constexpr int BWD_TI = 64, BWD_TJ = 256;
 static inline int bwd_rows(int64_t batch, int64_t n1, int64_t n2) {
     return batch * cdiv64(n1, BWD_TI) * cdiv64(n2, BWD_TJ) < 256 ? 16 : BWD_TI;
 }
+// The backward launch of a (batch, n1, n2) problem: the ONE place launch_bwd, bwd_ws_elems and nsgp_pairwise_bwd_plan take
+// it from.  Grid (ntj, nti, batch); the workspace holds ntj row-side, nti column-side and nti * ntj global partials.
+struct BwdPlan { int rows; int64_t nti, ntj; };
+static inline BwdPlan bwd_plan(int64_t batch, int64_t n1, int64_t n2) {
+    const int rows = bwd_rows(batch, n1, n2);
+    return {rows, cdiv64(n1, rows), cdiv64(n2, BWD_TJ)};
+}
 
 template <typename T, typename Op, int TI>
 __global__ __launch_bounds__(256) void pairwise_bwd_kernel(Op op, int64_t n1, int64_t n2,
@@ -604,8 +611,8 @@ __global__ __launch_bounds__(256) void reduce_all_kernel(const T* __restrict__ P
 }
 
 template <typename Op> size_t bwd_ws_elems(int64_t batch, int64_t n1, int64_t n2) {
-    const int64_t ntj = cdiv64(n2, BWD_TJ), nti = cdiv64(n1, bwd_rows(batch, n1, n2));
-    return (size_t)(batch * (ntj * n1 * Op::NR + nti * n2 * Op::NC + nti * ntj * Op::NG));
+    const BwdPlan p = bwd_plan(batch, n1, n2);
+    return (size_t)(batch * (p.ntj * n1 * Op::NR + p.nti * n2 * Op::NC + p.nti * p.ntj * Op::NG));
 }
 
 template <typename T, typename Op>
@@ -613,8 +620,9 @@ int launch_bwd(const Op& op, int64_t batch, int64_t n1, int64_t n2, const T* G, 
                const OutDesc<T>& rows, const OutDesc<T>& cols, const OutDesc<T>& globs,
                void* ws, size_t ws_bytes, void* stream) {
     if (n1 == 0 || n2 == 0 || batch == 0) return 0;
-    const int ti_rows = bwd_rows(batch, n1, n2);
-    const int64_t ntj = cdiv64(n2, BWD_TJ), nti = cdiv64(n1, ti_rows);
+    const BwdPlan plan = bwd_plan(batch, n1, n2);
+    const int ti_rows = plan.rows;
+    const int64_t ntj = plan.ntj, nti = plan.nti;
     if (ws_bytes < bwd_ws_elems<Op>(batch, n1, n2) * sizeof(T) || !ws) return -100;
     T* P1 = (T*)ws;
     T* P2 = P1 + batch * ntj * n1 * Op::NR;
@@ -856,6 +864,16 @@ int rbfper_bwd(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* pe
 }  // namespace
 
 extern "C" {
+
+int nsgp_pairwise_bwd_plan(int64_t batch, int64_t n1, int64_t n2, int* rows_per_wg, int64_t* nti, int64_t* ntj) {
+    if (batch < 0) return -1; if (n1 < 0) return -2; if (n2 < 0) return -3;
+    if (!rows_per_wg) return -4; if (!nti) return -5; if (!ntj) return -6;
+    *rows_per_wg = 0; *nti = 0; *ntj = 0;
+    if (batch == 0 || n1 == 0 || n2 == 0) return 0;          // nothing is launched
+    const BwdPlan p = bwd_plan(batch, n1, n2);
+    *rows_per_wg = p.rows; *nti = p.nti; *ntj = p.ntj;
+    return 0;
+}
 
 int nsgp_gibbs_build_fwd_f32(const float* x1, const float* x2, const float* l1, const float* l2, int64_t n1,
                              int64_t n2, int D, const float* os, const float* diag_add, float* K, int64_t ldk,

@@ -392,6 +392,23 @@ def ps2d_build_bwd(x1, x2, s1, s2, jitter, G):
     return g1, g2
 
 
+class PairwiseBwdPlan(NamedTuple):
+    """The launch every *_build_bwd makes (include/nsgp.h, nsgp_pairwise_bwd_plan)."""
+    rows: int
+    nti: int
+    ntj: int
+
+
+def pairwise_bwd_plan(batch, n1, n2):
+    """The backward launch of a (batch, n1, n2) build (batch = 1 for Gibbs and ps2d), as a PairwiseBwdPlan.  Host-side only:
+    nothing is launched and no GPU is needed."""
+    rows = ctypes.c_int(0)
+    nti, ntj = ctypes.c_int64(0), ctypes.c_int64(0)
+    ref = lambda v: ctypes.cast(ctypes.byref(v), ctypes.c_void_p)  # noqa: E731
+    _lib.call('nsgp_pairwise_bwd_plan', int(batch), int(n1), int(n2), ref(rows), ref(nti), ref(ntj))
+    return PairwiseBwdPlan(rows.value, nti.value, ntj.value)
+
+
 # --------------------------------------------------------------------------------------------
 # MFMA GEMM
 # --------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ def test_header_declares_the_hot_path_entry_points():
         for sfx in ('f32', 'f64'):
             assert f'nsgp_{stem}_{sfx}' in names, (stem, sfx)
     assert 'nsgp_adam_step_f32' in names and 'nsgp_abi_version' in names
+    assert 'nsgp_gemm_plan' in names and 'nsgp_pairwise_bwd_plan' in names          # host-side launch queries
 
 
 def test_library_loads_and_exports_every_declared_symbol():
@@ -33,6 +34,8 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.nsgp_potrf_workspace(1024, 3, 8) == 3 * 16 * 64 * 64 * 8
     assert lib.nsgp_gemm_workspace(1024, 40960, 1024, 1, 1, 4, 0) == 0
     assert lib.nsgp_gemm_workspace(1024, 1024, 40960, 1, 1, 4, 16) > 0
+    from nsgp import ops
+    assert tuple(ops.pairwise_bwd_plan(2, 1024, 1024)) == (16, 64, 4) and tuple(ops.pairwise_bwd_plan(1, 4096, 4096)) == (64, 64, 16)
 
 
 def test_no_signature_in_the_header_uses_torch_or_cxx_types():
