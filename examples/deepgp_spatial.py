@@ -35,7 +35,8 @@ def run_split(dataset, random_state, args, device):
     x_tr, y_tr, meanx, stdx, meany, stdy = dp.whitening_transform(data)
     train_x, train_y, test_x, test_y = dp.train_test_split(x_tr, y_tr, 0.8)
     torch.manual_seed(random_state)
-    model = m.DeepGP(args.layers, train_x.shape, num_inducing=args.inducing).to(device)
+    model = m.DeepGP(args.layers, train_x.shape, num_inducing=args.inducing,
+                     variational=getattr(args, 'variational', 'cholesky')).to(device)
     mll = DeepApproximateMLL(VariationalELBO(model.likelihood, model, train_x.shape[-2]))
     train_x, train_y, test_x, test_y = (t.to(device) for t in (train_x, train_y, test_x, test_y))
     loader = DataLoader(TensorDataset(train_x, train_y), batch_size=args.batch, shuffle=True)
@@ -84,6 +85,8 @@ def main():
     ap.add_argument('--samples', type=int, default=3)
     ap.add_argument('--inducing', type=int, default=250)
     ap.add_argument('--batch', type=int, default=315)
+    ap.add_argument('--variational', choices=('cholesky', 'mean_field'), default='cholesky',
+                    help="q(u) of every layer: a dense Cholesky factor (the reference) or a diagonal covariance")
     ap.add_argument('--lr', type=float, default=0.01)
     ap.add_argument('--out', default=None)
     ap.add_argument('--verbose', action='store_true')

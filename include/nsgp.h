@@ -470,6 +470,37 @@ int nsgp_rowdot_f32(const float* A, const float* g, int64_t batch, int64_t M, in
 int nsgp_rowdot_f64(const double* A, const double* g, int64_t batch, int64_t M, int64_t n, double* out,
                     void* stream);
 
+/* Mean-field q(u) = N(m, diag(s^2)) (gpytorch MeanFieldVariationalDistribution): there is no C = Lq^T A, the variance is
+ *   var[b,j] = base[b] + base_add + q[b,j],   q[b,j] = sum_k s2m1[b,k] A[b,k,j]^2,   s2m1 = s^2 - 1   (b, M).
+ *   diag_colsq: part_q[b,t,j] = sum over rows 32 t .. 32 t + 31 of s2m1 A^2, accumulated in float64 whatever A's type;
+ *       part_q:(batch, T, n) float64 with T >= nsgp_svgp_diag_tiles(M) = ceil(M / 32) (rows past it are written as zeros).
+ *   colstats_finalize_diag: mean = sum_t part_dot (+ the affine prior mean, arguments as colstats_finalize_affine; part_dot
+ *       (batch, tiles, n) from the first product's epilogue); var = base + base_add + sum_t part_q in float64, rounded once.
+ *   diag_bwd: Abar[b,k,j] = m[b,k] gmean[b,j] + 2 s2m1[b,k] A[b,k,j] gvar[b,j];  mbar[b,k] = sum_j A gmean;
+ *       tbar[b,k] = sum_j A^2 gvar (the gradient of s^2).  A is read once; the row sums are reduced in two stages in a
+ *       fixed order (float64 partials in ws, nsgp_svgp_diag_bwd_workspace bytes), no atomics.
+ * Each returns 0 without a launch when batch, M or n is 0. */
+size_t nsgp_svgp_diag_tiles(int64_t M);
+int nsgp_svgp_diag_colsq_f32(const float* A, const float* s2m1, int64_t batch, int64_t M, int64_t n, double* part_q,
+                             int64_t T, void* stream);
+int nsgp_svgp_diag_colsq_f64(const double* A, const double* s2m1, int64_t batch, int64_t M, int64_t n, double* part_q,
+                             int64_t T, void* stream);
+int nsgp_svgp_colstats_finalize_diag_f32(const float* part_dot, int64_t tiles, const double* part_q, int64_t qtiles,
+                                         const float* base, float base_add, int64_t batch, int64_t n, const float* x,
+                                         int64_t x_batch_stride, int64_t D, const float* w, int64_t w_batch_stride,
+                                         const float* c, int64_t c_batch_stride, float* mean, float* var, void* stream);
+int nsgp_svgp_colstats_finalize_diag_f64(const double* part_dot, int64_t tiles, const double* part_q, int64_t qtiles,
+                                         const double* base, double base_add, int64_t batch, int64_t n, const double* x,
+                                         int64_t x_batch_stride, int64_t D, const double* w, int64_t w_batch_stride,
+                                         const double* c, int64_t c_batch_stride, double* mean, double* var, void* stream);
+size_t nsgp_svgp_diag_bwd_workspace(int64_t batch, int64_t M, int64_t n);
+int nsgp_svgp_diag_bwd_f32(const float* A, const float* m, const float* s2m1, const float* gmean, const float* gvar,
+                           int64_t batch, int64_t M, int64_t n, float* Abar, float* mbar, float* tbar, void* ws,
+                           size_t ws_bytes, void* stream);
+int nsgp_svgp_diag_bwd_f64(const double* A, const double* m, const double* s2m1, const double* gmean, const double* gvar,
+                           int64_t batch, int64_t M, int64_t n, double* Abar, double* mbar, double* tbar, void* ws,
+                           size_t ws_bytes, void* stream);
+
 /* DeepGPLayer sampling:  h[s,i,c] = mean[c,s?,i] + sqrt(var[c,s?,i]) * eps[s,i,c]
  *   mean/var are (b, ns, n) with ns == 1 (deterministic first layer, broadcast over S) or ns == S.
  *   backward accumulates gmean/gvar (b, ns, n) from gh (S,n,b). */
@@ -557,6 +588,18 @@ int nsgp_kl_whitened_total_bwd_f32(const float* m, const float* Lq, int64_t batc
                                    const float* gout, float* gm, float* gLq, void* stream);
 int nsgp_kl_whitened_total_bwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double scale,
                                    const double* gout, double* gm, double* gLq, void* stream);
+/* Mean-field twin: KL(N(m, diag(s2)) || N(0, I)) = 1/2 sum_k (s2_k + m_k^2 - 1 - log s2_k), m, s2:(batch, M).
+ *   total_acc_fwd: out[0] = addin[0] + scale * sum_b KL_b (addin may be NULL; ws: nsgp_reduce_workspace bytes);
+ *   total_bwd:     gm = scale gout[0] m,  gs2 = scale gout[0] (1 - 1 / s2) / 2,  gout a 1-element DEVICE scalar.
+ * batch == 0 or M == 0: returns 0 without a launch (out is not written). */
+int nsgp_kl_meanfield_total_acc_fwd_f32(const float* m, const float* s2, int64_t batch, int64_t M, float scale,
+                                        const float* addin, float* out, void* ws, size_t wsb, void* stream);
+int nsgp_kl_meanfield_total_acc_fwd_f64(const double* m, const double* s2, int64_t batch, int64_t M, double scale,
+                                        const double* addin, double* out, void* ws, size_t wsb, void* stream);
+int nsgp_kl_meanfield_total_bwd_f32(const float* m, const float* s2, int64_t batch, int64_t M, float scale,
+                                    const float* gout, float* gm, float* gs2, void* stream);
+int nsgp_kl_meanfield_total_bwd_f64(const double* m, const double* s2, int64_t batch, int64_t M, double scale,
+                                    const double* gout, double* gm, double* gs2, void* stream);
 int nsgp_kl_whitened_fwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float* out,
                              void* ws, size_t ws_bytes, void* stream);
 int nsgp_kl_whitened_bwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float gout,

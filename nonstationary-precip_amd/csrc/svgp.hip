@@ -704,6 +704,270 @@ static int dsvi_obj_bwd_impl(const T* y, const T* mu, const T* v, const T* noise
     return nsgp_launch_status();
 }
 
+// ---- mean-field q(u) = N(m, diag(s^2)): column statistics, their adjoint and the KL term -------------------------------
+// There is no C = Lq^T A: var_j = base + base_add + sum_k (s_k^2 - 1) A_kj^2 is one pass over A.  The sum is taken in
+// float64 whatever A's type is (its terms have both signs once q(u) has trained) and meets base in float64.
+constexpr int DIAG_ROWS = 32;            // rows of A per partial (nsgp_svgp_diag_tiles)
+constexpr int DIAG_BWD_COLS = 4096;      // columns of A per workgroup of the backward pass
+
+template <typename T, int V> struct VecOf;
+template <> struct VecOf<float, 4> { using type = float4; };
+template <> struct VecOf<double, 2> { using type = double2; };
+
+// V consecutive elements at p (V > 1: p is 16-byte aligned)
+template <typename T, int V> __device__ __forceinline__ void ld_vec(const T* __restrict__ p, T (&v)[V]) {
+    if constexpr (V == 1) {
+        v[0] = p[0];
+    } else {
+        const typename VecOf<T, V>::type t = *reinterpret_cast<const typename VecOf<T, V>::type*>(p);
+        v[0] = t.x; v[1] = t.y;
+        if constexpr (V == 4) { v[2] = t.z; v[3] = t.w; }
+    }
+}
+template <typename T, int V> __device__ __forceinline__ void st_vec(T* __restrict__ p, const T (&v)[V]) {
+    if constexpr (V == 1) {
+        p[0] = v[0];
+    } else {
+        typename VecOf<T, V>::type t;
+        t.x = v[0]; t.y = v[1];
+        if constexpr (V == 4) { t.z = v[2]; t.w = v[3]; }
+        *reinterpret_cast<typename VecOf<T, V>::type*>(p) = t;
+    }
+}
+
+// part[b,t,j] = sum_{k in tile t} s2m1[b,k] A[b,k,j]^2.  grid (column groups, T, batch); a lane owns V columns, a
+// workgroup DIAG_ROWS rows (tiles past the last row write zeros: every row of the buffer is written).
+template <typename T, int V>
+__global__ __launch_bounds__(256) void diag_colsq_kernel(const T* __restrict__ A, const T* __restrict__ s2m1, int64_t M,
+                                                         int64_t n, double* __restrict__ part) {
+    const int64_t b = blockIdx.z, t = blockIdx.y;
+    const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (j >= n) return;                                  // (V > 1: n % V == 0, so j + V <= n)
+    const int64_t k0 = t * DIAG_ROWS, k1 = (k0 + DIAG_ROWS) < M ? (k0 + DIAG_ROWS) : M;
+    const T* Ab = A + b * M * n + j;
+    const T* sb = s2m1 + b * M;
+    double acc[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = 0.0;
+#pragma unroll 8
+    for (int64_t k = k0; k < k1; ++k) {
+        T a[V];
+        ld_vec<T, V>(Ab + k * n, a);
+        const double s = (double)sb[k];
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[v] = __builtin_fma(s * (double)a[v], (double)a[v], acc[v]);
+    }
+    double* out = part + (b * gridDim.y + t) * n + j;
+#pragma unroll
+    for (int v = 0; v < V; ++v) out[v] = acc[v];
+}
+
+// mean as colstats_finalize_kernel (same order, same type); var = (base + base_add + sum_t part_q) in float64, rounded once
+template <typename T>
+__global__ void colstats_finalize_diag_kernel(const T* __restrict__ pdot, int64_t tiles, const double* __restrict__ pq,
+                                              int64_t qtiles, const T* __restrict__ base, T base_add, int64_t batch,
+                                              int64_t n, const T* __restrict__ x, int64_t sxb, int D,
+                                              const T* __restrict__ w, int64_t swb, const T* __restrict__ c, int64_t scb,
+                                              T* __restrict__ mean, T* __restrict__ var) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= batch * n) return;
+    const int64_t b = idx / n, j = idx % n;
+    T sm = T(0);
+    for (int64_t t = 0; t < tiles; ++t) sm += pdot[(b * tiles + t) * n + j];
+    double q = 0.0;
+    for (int64_t t = 0; t < qtiles; ++t) q += pq[(b * qtiles + t) * n + j];
+    if (w) {
+        const T* xr = x + b * sxb + j * D;
+        const T* wr = w + b * swb;
+        T mu = T(0);
+        for (int d = 0; d < D; ++d) mu += xr[d] * wr[d];
+        sm += mu;
+    }
+    if (c) sm += c[b * scb];
+    mean[idx] = sm;
+    var[idx] = (T)(((double)base[b] + (double)base_add) + q);
+}
+
+// Abar = m gmean^T + 2 diag(s2m1) A diag(gvar), and the partial row sums of A gmean and A^2 gvar over DIAG_BWD_COLS columns:
+// grid (M, column chunks, batch); part[((b M + k) chunks + c) 2 + {0, 1}] in float64
+template <typename T, int V>
+__global__ __launch_bounds__(256) void diag_bwd_kernel(const T* __restrict__ A, const T* __restrict__ m,
+                                                       const T* __restrict__ s2m1, const T* __restrict__ gmean,
+                                                       const T* __restrict__ gvar, int64_t M, int64_t n,
+                                                       T* __restrict__ Abar, double* __restrict__ part) {
+    __shared__ double lds[4];
+    const int64_t k = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const int64_t row = (b * M + k) * n;
+    const T mk = m[b * M + k], s2 = T(2) * s2m1[b * M + k];
+    const T* gm = gmean + b * n;
+    const T* gv = gvar + b * n;
+    const int64_t j0 = c * DIAG_BWD_COLS, j1 = (j0 + DIAG_BWD_COLS) < n ? (j0 + DIAG_BWD_COLS) : n;
+    T am = T(0), at = T(0);
+#pragma unroll 4
+    for (int64_t j = j0 + (int64_t)threadIdx.x * V; j < j1; j += 256 * V) {
+        T a[V], g1[V], g2[V], o[V];
+        ld_vec<T, V>(A + row + j, a);
+        ld_vec<T, V>(gm + j, g1);
+        ld_vec<T, V>(gv + j, g2);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const T ag = a[v] * g2[v];
+            o[v] = mk * g1[v] + s2 * ag;
+            am += a[v] * g1[v];
+            at += a[v] * ag;
+        }
+        st_vec<T, V>(Abar + row + j, o);
+    }
+    const double sm = block_sum_256((double)am, lds);
+    const double st = block_sum_256((double)at, lds);
+    if (threadIdx.x == 0) {
+        double* p = part + ((b * M + k) * gridDim.y + c) * 2;
+        p[0] = sm; p[1] = st;
+    }
+}
+
+template <typename T>
+__global__ void diag_bwd_final_kernel(const double* __restrict__ part, int64_t rows, int64_t chunks, T* __restrict__ mbar,
+                                      T* __restrict__ tbar) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    double sm = 0.0, st = 0.0;
+    for (int64_t c = 0; c < chunks; ++c) { sm += part[(r * chunks + c) * 2]; st += part[(r * chunks + c) * 2 + 1]; }
+    mbar[r] = (T)sm;
+    tbar[r] = (T)st;
+}
+
+// part[blk] = sum over a strided share of the batch * M elements of (s2 - 1) - log s2 + m^2  (twice the KL)
+template <typename T>
+__global__ __launch_bounds__(256) void kl_diag_part_kernel(const T* __restrict__ m, const T* __restrict__ s2, int64_t tot,
+                                                           T* __restrict__ part) {
+    __shared__ T lds[4];
+    T acc = T(0);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < tot; i += (int64_t)gridDim.x * 256) {
+        const T v = s2[i], mm = m[i];
+        acc += ((v - T(1)) - t_log(v)) + mm * mm;
+    }
+    acc = block_sum_256(acc, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// out[0] = (addin ? addin[0] : 0) + scale * sum(part): the scaled term is rounded on its own (no contraction into the
+// addition), so that chaining onto a running scalar adds exactly the value the un-chained call returns
+template <typename T>
+__global__ __launch_bounds__(256) void kl_diag_final_kernel(const T* __restrict__ part, int64_t nparts, T scale,
+                                                            const T* __restrict__ addin, T* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ T lds[4];
+    T s = T(0);
+    for (int64_t t = threadIdx.x; t < nparts; t += 256) s += part[t];
+    s = block_sum_256(s, lds);
+    if (threadIdx.x == 0) {
+        const T r = scale * s;
+        out[0] = addin ? addin[0] + r : r;
+    }
+}
+
+template <typename T>
+__global__ void kl_diag_bwd_kernel(const T* __restrict__ m, const T* __restrict__ s2, int64_t tot, T scale,
+                                   const T* __restrict__ gout, T* __restrict__ gm, T* __restrict__ gs2) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= tot) return;
+    const T go = scale * gout[0];
+    gm[i] = go * m[i];
+    gs2[i] = T(0.5) * go * (T(1) - T(1) / s2[i]);
+}
+
+template <typename T> static bool vec_ok(const void* p) { return ((uintptr_t)p % 16) == 0; }
+
+template <typename T>
+static int diag_colsq_impl(const T* A, const T* s2m1, int64_t batch, int64_t M, int64_t n, double* part, int64_t Tq,
+                           void* stream) {
+    if (!A) return -1; if (!s2m1) return -2; if (batch < 0 || batch > 65535) return -3; if (M < 0) return -4;
+    if (n < 0) return -5; if (!part) return -6; if (Tq < cdiv64(M, DIAG_ROWS) || Tq > 65535) return -7;
+    if (batch == 0 || M == 0 || n == 0) return 0;
+    constexpr int V = 16 / sizeof(T);
+    hipStream_t st = (hipStream_t)stream;
+    if (n % V == 0 && vec_ok<T>(A)) {
+        if (cdiv64(n, 256 * V) > 2147483647LL) return -5;
+        hipLaunchKernelGGL((diag_colsq_kernel<T, V>), dim3((unsigned)cdiv64(n, 256 * V), (unsigned)Tq, (unsigned)batch),
+                           dim3(256), 0, st, A, s2m1, M, n, part);
+    } else {
+        if (cdiv64(n, 256) > 2147483647LL) return -5;
+        hipLaunchKernelGGL((diag_colsq_kernel<T, 1>), dim3((unsigned)cdiv64(n, 256), (unsigned)Tq, (unsigned)batch),
+                           dim3(256), 0, st, A, s2m1, M, n, part);
+    }
+    return nsgp_launch_status();
+}
+
+template <typename T>
+static int finalize_diag_impl(const T* part_dot, int64_t tiles, const double* part_q, int64_t qtiles, const T* base,
+                              T base_add, int64_t batch, int64_t n, const T* x, int64_t sxb, int64_t D, const T* w,
+                              int64_t swb, const T* c, int64_t scb, T* mean, T* var, void* stream) {
+    if (!part_dot) return -1; if (tiles < 0) return -2; if (!part_q) return -3; if (qtiles < 0) return -4;
+    if (!base) return -5; if (batch < 0) return -7; if (n < 0) return -8;
+    if (w && !x) return -9; if (sxb < 0) return -10; if (D < 0 || D > NSGP_MAX_DIM || (w && D == 0)) return -11;
+    if (swb < 0) return -13; if (scb < 0) return -15; if (!mean) return -16; if (!var) return -17;
+    if (batch * n == 0) return 0;
+    if (cdiv64(batch * n, 256) > 2147483647LL) return -8;
+    hipLaunchKernelGGL((colstats_finalize_diag_kernel<T>), dim3((unsigned)cdiv64(batch * n, 256)), dim3(256), 0,
+                       (hipStream_t)stream, part_dot, tiles, part_q, qtiles, base, base_add, batch, n, x, sxb, (int)D, w,
+                       swb, c, scb, mean, var);
+    return nsgp_launch_status();
+}
+
+static inline size_t diag_bwd_ws(int64_t batch, int64_t M, int64_t n) {
+    if (batch <= 0 || M <= 0 || n <= 0) return 0;
+    return (size_t)(batch * M * cdiv64(n, DIAG_BWD_COLS)) * 2 * sizeof(double);
+}
+
+template <typename T>
+static int diag_bwd_impl(const T* A, const T* m, const T* s2m1, const T* gmean, const T* gvar, int64_t batch, int64_t M,
+                         int64_t n, T* Abar, T* mbar, T* tbar, void* ws, size_t wsb, void* stream) {
+    if (!A) return -1; if (!m) return -2; if (!s2m1) return -3; if (!gmean) return -4; if (!gvar) return -5;
+    if (batch < 0 || batch > 65535) return -6; if (M < 0 || M > 2147483647LL) return -7; if (n < 0) return -8;
+    if (!Abar) return -9; if (!mbar) return -10; if (!tbar) return -11;
+    if (batch == 0 || M == 0 || n == 0) return 0;
+    const int64_t chunks = cdiv64(n, DIAG_BWD_COLS);
+    if (chunks > 65535) return -8;
+    if (!ws || ((uintptr_t)ws % 8) != 0) return -12; if (wsb < diag_bwd_ws(batch, M, n)) return -13;
+    constexpr int V = 16 / sizeof(T);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)M, (unsigned)chunks, (unsigned)batch);
+    if (n % V == 0 && vec_ok<T>(A) && vec_ok<T>(Abar) && vec_ok<T>(gmean) && vec_ok<T>(gvar))
+        hipLaunchKernelGGL((diag_bwd_kernel<T, V>), grid, dim3(256), 0, st, A, m, s2m1, gmean, gvar, M, n, Abar, (double*)ws);
+    else
+        hipLaunchKernelGGL((diag_bwd_kernel<T, 1>), grid, dim3(256), 0, st, A, m, s2m1, gmean, gvar, M, n, Abar, (double*)ws);
+    hipLaunchKernelGGL((diag_bwd_final_kernel<T>), dim3((unsigned)cdiv64(batch * M, 256)), dim3(256), 0, st,
+                       (const double*)ws, batch * M, chunks, mbar, tbar);
+    return nsgp_launch_status();
+}
+
+template <typename T>
+static int kl_diag_fwd_impl(const T* m, const T* s2, int64_t batch, int64_t M, T scale, const T* addin, T* out, void* ws,
+                            size_t wsb, void* stream) {
+    if (!m) return -1; if (!s2) return -2; if (batch < 0) return -3; if (M < 0) return -4; if (!out) return -7;
+    if (batch == 0 || M == 0) return 0;
+    int64_t nblk = cdiv64(batch * M, 1024); if (nblk > 256) nblk = 256;
+    if (!ws) return -8; if (wsb < (size_t)nblk * sizeof(T)) return -9;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL((kl_diag_part_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, st, m, s2, batch * M, (T*)ws);
+    hipLaunchKernelGGL((kl_diag_final_kernel<T>), dim3(1), dim3(256), 0, st, (const T*)ws, nblk, T(0.5) * scale, addin, out);
+    return nsgp_launch_status();
+}
+
+template <typename T>
+static int kl_diag_bwd_impl(const T* m, const T* s2, int64_t batch, int64_t M, T scale, const T* gout, T* gm, T* gs2,
+                            void* stream) {
+    if (!m) return -1; if (!s2) return -2; if (batch < 0) return -3; if (M < 0) return -4; if (!gout) return -6;
+    if (!gm) return -7; if (!gs2) return -8;
+    const int64_t tot = batch * M;
+    if (tot == 0) return 0;
+    if (cdiv64(tot, 256) > 2147483647LL) return -4;
+    hipLaunchKernelGGL((kl_diag_bwd_kernel<T>), dim3((unsigned)cdiv64(tot, 256)), dim3(256), 0, (hipStream_t)stream, m, s2,
+                       tot, scale, gout, gm, gs2);
+    return nsgp_launch_status();
+}
+
 }  // namespace
 
 template <typename T, typename TP = T>
@@ -891,6 +1155,57 @@ int nsgp_rowdot_f64(const double* A, const double* g, int64_t batch, int64_t M, 
     return nsgp_launch_status();
 }
 
+/* mean-field q(u): column statistics, their adjoint, KL (nsgp.svgp.SVGPMeanFieldLayerFn, nsgp.ops.KlMeanFieldTotalFn) */
+size_t nsgp_svgp_diag_tiles(int64_t M) { return M > 0 ? (size_t)cdiv64(M, DIAG_ROWS) : 0; }
+int nsgp_svgp_diag_colsq_f32(const float* A, const float* s2m1, int64_t batch, int64_t M, int64_t n, double* part_q,
+                             int64_t T, void* stream) {
+    return diag_colsq_impl<float>(A, s2m1, batch, M, n, part_q, T, stream);
+}
+int nsgp_svgp_diag_colsq_f64(const double* A, const double* s2m1, int64_t batch, int64_t M, int64_t n, double* part_q,
+                             int64_t T, void* stream) {
+    return diag_colsq_impl<double>(A, s2m1, batch, M, n, part_q, T, stream);
+}
+int nsgp_svgp_colstats_finalize_diag_f32(const float* part_dot, int64_t tiles, const double* part_q, int64_t qtiles,
+                                         const float* base, float base_add, int64_t batch, int64_t n, const float* x,
+                                         int64_t x_batch_stride, int64_t D, const float* w, int64_t w_batch_stride,
+                                         const float* c, int64_t c_batch_stride, float* mean, float* var, void* stream) {
+    return finalize_diag_impl<float>(part_dot, tiles, part_q, qtiles, base, base_add, batch, n, x, x_batch_stride, D, w,
+                                     w_batch_stride, c, c_batch_stride, mean, var, stream);
+}
+int nsgp_svgp_colstats_finalize_diag_f64(const double* part_dot, int64_t tiles, const double* part_q, int64_t qtiles,
+                                         const double* base, double base_add, int64_t batch, int64_t n, const double* x,
+                                         int64_t x_batch_stride, int64_t D, const double* w, int64_t w_batch_stride,
+                                         const double* c, int64_t c_batch_stride, double* mean, double* var, void* stream) {
+    return finalize_diag_impl<double>(part_dot, tiles, part_q, qtiles, base, base_add, batch, n, x, x_batch_stride, D, w,
+                                      w_batch_stride, c, c_batch_stride, mean, var, stream);
+}
+size_t nsgp_svgp_diag_bwd_workspace(int64_t batch, int64_t M, int64_t n) { return diag_bwd_ws(batch, M, n); }
+int nsgp_svgp_diag_bwd_f32(const float* A, const float* m, const float* s2m1, const float* gmean, const float* gvar,
+                           int64_t batch, int64_t M, int64_t n, float* Abar, float* mbar, float* tbar, void* ws,
+                           size_t ws_bytes, void* stream) {
+    return diag_bwd_impl<float>(A, m, s2m1, gmean, gvar, batch, M, n, Abar, mbar, tbar, ws, ws_bytes, stream);
+}
+int nsgp_svgp_diag_bwd_f64(const double* A, const double* m, const double* s2m1, const double* gmean, const double* gvar,
+                           int64_t batch, int64_t M, int64_t n, double* Abar, double* mbar, double* tbar, void* ws,
+                           size_t ws_bytes, void* stream) {
+    return diag_bwd_impl<double>(A, m, s2m1, gmean, gvar, batch, M, n, Abar, mbar, tbar, ws, ws_bytes, stream);
+}
+int nsgp_kl_meanfield_total_acc_fwd_f32(const float* m, const float* s2, int64_t batch, int64_t M, float scale,
+                                        const float* addin, float* out, void* ws, size_t wsb, void* stream) {
+    return kl_diag_fwd_impl<float>(m, s2, batch, M, scale, addin, out, ws, wsb, stream);
+}
+int nsgp_kl_meanfield_total_acc_fwd_f64(const double* m, const double* s2, int64_t batch, int64_t M, double scale,
+                                        const double* addin, double* out, void* ws, size_t wsb, void* stream) {
+    return kl_diag_fwd_impl<double>(m, s2, batch, M, scale, addin, out, ws, wsb, stream);
+}
+int nsgp_kl_meanfield_total_bwd_f32(const float* m, const float* s2, int64_t batch, int64_t M, float scale,
+                                    const float* gout, float* gm, float* gs2, void* stream) {
+    return kl_diag_bwd_impl<float>(m, s2, batch, M, scale, gout, gm, gs2, stream);
+}
+int nsgp_kl_meanfield_total_bwd_f64(const double* m, const double* s2, int64_t batch, int64_t M, double scale,
+                                    const double* gout, double* gm, double* gs2, void* stream) {
+    return kl_diag_bwd_impl<double>(m, s2, batch, M, scale, gout, gm, gs2, stream);
+}
 
 /* scalar forms used by the fused ELBO tail (nsgp.ops.GaussEllTotalFn / KlWhitenedTotalFn) */
 int nsgp_gauss_ell_total_fwd_f32(const float* y, const float* mu, const float* v, const float* noise, int64_t S,

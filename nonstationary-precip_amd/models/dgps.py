@@ -7,7 +7,8 @@ Same surface (reference file:line):
   ExactGPModel(train_x, train_y, likelihood, kernel)                                    :113-122
 Reference quirks kept: the hidden layers are ONE tied layer object repeated
 num_layers times, and predict() returns only the last batch's distribution.  Additions (keyword-only,
-defaults reproduce the reference): DeepGP(..., num_inducing=250, tie_layers=True).
+defaults reproduce the reference): DeepGP(..., num_inducing=250, tie_layers=True, variational='cholesky');
+variational='mean_field' gives every layer a MeanFieldVariationalDistribution.
 """
 import torch
 
@@ -18,18 +19,22 @@ from nsgp.gp.kernels import RBFKernel, ScaleKernel
 from nsgp.gp.likelihoods import GaussianLikelihood
 from nsgp.gp.means import ConstantMean, LinearMean
 from nsgp.gp.models import DeepGPLayer, DeepGP as _DeepGPBase, ExactGP
-from nsgp.gp.variational import CholeskyVariationalDistribution, VariationalStrategy
+from nsgp.gp.variational import CholeskyVariationalDistribution, MeanFieldVariationalDistribution, VariationalStrategy
 
 num_output_dims = 2
+VARIATIONAL_DISTRIBUTIONS = {'cholesky': CholeskyVariationalDistribution, 'mean_field': MeanFieldVariationalDistribution}
 
 
 class DeepGPHiddenLayer(DeepGPLayer):
-    """One whitened SVGP layer: Z ~ randn, q(u) = N(m, Lq Lq^T), ScaleKernel(RBF-ARD)."""
+    """One whitened SVGP layer: Z ~ randn, q(u) = N(m, Lq Lq^T) -- or N(m, diag(s^2)) with variational='mean_field' --,
+    ScaleKernel(RBF-ARD)."""
 
-    def __init__(self, input_dims, output_dims, num_inducing=250, mean_type='constant'):
+    def __init__(self, input_dims, output_dims, num_inducing=250, mean_type='constant', variational='cholesky'):
+        if variational not in VARIATIONAL_DISTRIBUTIONS:
+            raise ValueError(f'variational must be one of {sorted(VARIATIONAL_DISTRIBUTIONS)}, got {variational!r}')
         batch_shape = torch.Size([]) if output_dims is None else torch.Size([output_dims])
         Z = torch.randn(*batch_shape, num_inducing, input_dims)
-        q_u = CholeskyVariationalDistribution(num_inducing_points=num_inducing, batch_shape=batch_shape)
+        q_u = VARIATIONAL_DISTRIBUTIONS[variational](num_inducing_points=num_inducing, batch_shape=batch_shape)
         strategy = VariationalStrategy(self, Z, q_u, learn_inducing_locations=True)
         super().__init__(strategy, input_dims, output_dims)
         self.mean_module = ConstantMean(batch_shape=batch_shape) if mean_type == 'constant' \
@@ -52,16 +57,17 @@ class DeepGPHiddenLayer(DeepGPLayer):
 
 
 class DeepGP(_DeepGPBase):
-    def __init__(self, num_layers, train_x_shape, *, num_inducing=250, tie_layers=True):
+    def __init__(self, num_layers, train_x_shape, *, num_inducing=250, tie_layers=True, variational='cholesky'):
         hidden = DeepGPHiddenLayer(input_dims=train_x_shape[-1], output_dims=num_output_dims,
-                                   num_inducing=num_inducing, mean_type='linear')
+                                   num_inducing=num_inducing, mean_type='linear', variational=variational)
         last = DeepGPHiddenLayer(input_dims=hidden.output_dims, output_dims=None,
-                                 num_inducing=num_inducing, mean_type='constant')
+                                 num_inducing=num_inducing, mean_type='constant', variational=variational)
         super().__init__()
         if tie_layers:
             stack = [hidden for _ in range(num_layers)]
         else:
-            stack = [hidden] + [DeepGPHiddenLayer(hidden.output_dims, num_output_dims, num_inducing, 'linear')
+            stack = [hidden] + [DeepGPHiddenLayer(hidden.output_dims, num_output_dims, num_inducing, 'linear',
+                                                  variational=variational)
                                 for _ in range(num_layers - 1)]
         self.layers = torch.nn.ModuleList(stack)
         self.last_layer = last

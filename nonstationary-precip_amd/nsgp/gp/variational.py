@@ -1,8 +1,10 @@
 """Whitened variational GP approximation [gpytorch.variational recalled, SURVEY A.3]:
 CholeskyVariationalDistribution (variational_mean (*batch,M) init 0 (+N(0,1e-3^2) on first use),
-chol_variational_covar (*batch,M,M) init I) and VariationalStrategy (learnable inducing_points),
-with state-dict keys `variational_strategy.inducing_points`,
-`variational_strategy._variational_distribution.{variational_mean,chol_variational_covar}`.
+chol_variational_covar (*batch,M,M) init I), MeanFieldVariationalDistribution (variational_mean as above,
+_variational_stddev (*batch,M) init 1; q(u) = N(m, diag(s^2)), s = |_variational_stddev| clamped at 1e-8) and
+VariationalStrategy (learnable inducing_points), with state-dict keys `variational_strategy.inducing_points`,
+`variational_strategy._variational_distribution.{variational_mean,chol_variational_covar}` /
+`{variational_mean,_variational_stddev}`.
 
 The marginals are ONE fused autograd node on the MI355X (nsgp.svgp.SVGPLayerFn): Kzz / Cholesky /
 inverse once per call in float64, then MFMA GEMMs -- no per-sample recomputation."""
@@ -13,7 +15,7 @@ from ..svgp import svgp_marginal, whiten, VAR_JITTER
 from . import settings
 from .distributions import MultivariateNormal
 from .kernels import RBFKernel, ScaleKernel
-from .lazy import CholLazyTensor
+from .lazy import CholLazyTensor, DiagLazyTensor
 from .means import ConstantMean, LinearMean, ZeroMean
 from .module import Module
 
@@ -48,6 +50,31 @@ class CholeskyVariationalDistribution(_VariationalDistribution):
             self.chol_variational_covar.copy_(eye.expand_as(self.chol_variational_covar))
 
 
+class MeanFieldVariationalDistribution(_VariationalDistribution):
+    """q(u) = N(m, diag(s^2)): M scale parameters per GP instead of the M (M + 1) / 2 of a Cholesky factor."""
+
+    def __init__(self, num_inducing_points, batch_shape=torch.Size(), mean_init_std=1e-3, **kwargs):
+        super().__init__(num_inducing_points, batch_shape, mean_init_std)
+        M = num_inducing_points
+        self.register_parameter('variational_mean', torch.nn.Parameter(torch.zeros(*self.batch_shape, M)))
+        self.register_parameter('_variational_stddev', torch.nn.Parameter(torch.ones(*self.batch_shape, M)))
+
+    @property
+    def variational_stddev(self):
+        # (gradient of the raw parameter: sign(raw) s-bar, and zero where the clamp is active -- plain autograd)
+        return self._variational_stddev.abs().clamp_min(1e-8)
+
+    def forward(self):
+        return MultivariateNormal(self.variational_mean, DiagLazyTensor(self.variational_stddev.pow(2)))
+
+    def initialize_variational_distribution(self, prior_dist=None):
+        """Whitened prior is N(0, I): mean <- 0 + N(0, mean_init_std^2), stddev <- 1."""
+        with torch.no_grad():
+            self.variational_mean.zero_()
+            self.variational_mean.add_(torch.randn_like(self.variational_mean), alpha=self.mean_init_std)
+            self._variational_stddev.fill_(1.0)
+
+
 class _VariationalStrategy(Module):
     def __init__(self, model, inducing_points, variational_distribution, learn_inducing_locations=True):
         super().__init__()
@@ -77,12 +104,23 @@ class _VariationalStrategy(Module):
 class VariationalStrategy(_VariationalStrategy):
     """Whitened strategy: prior on the whitened inducing values is N(0, I)."""
 
-    def _flat_params(self):
+    @property
+    def _mean_field(self):
+        return isinstance(self._variational_distribution, MeanFieldVariationalDistribution)
+
+    def _flat_params(self, q=True):
+        """(Z, ls, os, m, Lq) with a leading batch dimension; for a mean-field q(u) the last entry is s^2:(b,M), formed
+        from the raw parameter with plain torch ops (q=False: m and the last entry are None -- kernel parameters only)."""
         Z = self.inducing_points
-        m = self._variational_distribution.variational_mean
-        Lq = self._variational_distribution.chol_variational_covar
+        m = Lq = None
+        if q:
+            m = self._variational_distribution.variational_mean
+            Lq = self._variational_distribution.variational_stddev.square() if self._mean_field \
+                else self._variational_distribution.chol_variational_covar
         if Z.dim() == 2:
-            Z, m, Lq = Z.unsqueeze(0), m.unsqueeze(0), Lq.unsqueeze(0)
+            Z = Z.unsqueeze(0)
+            if q:
+                m, Lq = m.unsqueeze(0), Lq.unsqueeze(0)
         b, M, D = Z.shape
         kern = self.model.covar_module
         if not (isinstance(kern, ScaleKernel) and isinstance(kern.base_kernel, RBFKernel)):
@@ -97,7 +135,7 @@ class VariationalStrategy(_VariationalStrategy):
 
     def whiten_group(self):
         """(Z, ls, os) of this layer's GPs for the batched Kzz -> Cholesky -> inverse chain."""
-        Z, ls, os_, _, _ = self._flat_params()
+        Z, ls, os_, _, _ = self._flat_params(q=False)
         return Z, ls.contiguous(), os_.contiguous()
 
     def marginals(self, x_flat, feeds_next=False):
@@ -112,10 +150,11 @@ class VariationalStrategy(_VariationalStrategy):
             Z, ls, os_ = routed                          # same values; gradients return through the whitening node
         b = Z.shape[0]
         fused, mean_w, mean_c = self._affine_prior_mean(b, x_flat.shape[-1])
-        mean, var, _info = svgp_marginal(x_flat, Z, ls.contiguous(), os_.contiguous(), m, Lq, jitter=jitter,
+        q = dict(s2=Lq) if self._mean_field else dict(Lq=Lq)
+        mean, var, _info = svgp_marginal(x_flat, Z, ls.contiguous(), os_.contiguous(), m, jitter=jitter,
                                          chol_bwd_f64=settings.chol_bwd_f64.on(), W64=W64, mean_w=mean_w,
                                          mean_c=mean_c, W64f=getattr(self, '_W64f_shared', None) if W64 is not None else None,
-                                         kzx_f64=bool(feeds_next) and settings.hidden_kzx_f64.on())
+                                         kzx_f64=bool(feeds_next) and settings.hidden_kzx_f64.on(), **q)
         if fused:
             return mean, var
         xin = x_flat if b == 1 and self.inducing_points.dim() == 2 else x_flat.unsqueeze(0).expand(b, *x_flat.shape)
@@ -155,15 +194,20 @@ class VariationalStrategy(_VariationalStrategy):
                 A = ops.cast(ops.gemm(W64, ops.cast(Kzx, torch.float64), flags=ops.GEMM_A_LOWER), torch.float32)
             else:
                 A = ops.gemm(ops.cast(W64, x.dtype), Kzx, flags=ops.GEMM_A_LOWER)
-            C = ops.gemm(Lq[0], A, ta=True, flags=ops.GEMM_A_UPPER)
+            if self._mean_field:                                           # C = diag(s) A: a row scaling
+                C = Lq[0].sqrt().unsqueeze(-1) * A
+            else:
+                C = ops.gemm(Lq[0], A, ta=True, flags=ops.GEMM_A_UPPER)
             Kxx = ops.rbf_build(x, x, lsS, osS, diag_add=VAR_JITTER)
             ops.gemm(C, C, ta=True, beta=1.0, out=Kxx)
             ops.gemm(A, A, ta=True, alpha=-1.0, beta=1.0, out=Kxx)
             return Kxx
 
     def kl_divergence(self):
-        """KL(N(m, Lq Lq^T) || N(0, I)) per batch element, shape batch_shape."""
+        """KL(q(u) || N(0, I)) summed over the batch; q(u) = N(m, Lq Lq^T) or mean-field N(m, diag(s^2))."""
         m = self._variational_distribution.variational_mean
+        if self._mean_field:
+            return ops.KlMeanFieldFn.apply(m, self._variational_distribution.variational_stddev.square())
         Lq = self._variational_distribution.chol_variational_covar
         return ops.KlWhitenedFn.apply(m, Lq)
 

@@ -743,7 +743,7 @@ def _project_a_i8(W64f, kZ, kx, kls, kos, m, A, part_dot, part_sq, T, p64, plane
 class ProjectionPlan(NamedTuple):
     """What one forward projection launches and how its column-statistic partials are laid out (`svgp_projection_plan`)."""
     first: str                  # arithmetic of A = W Kzx: 'f32' | 'f64acc' | 'f64acc_b64' | 'kzx_fused' | 'i8' | 'bf16'
-    second: str                 # arithmetic of C = Lq^T A: 'f32' | 'f64acc_t' | 'bf16'
+    second: str                 # arithmetic of C = Lq^T A: 'f32' | 'f64acc_t' | 'bf16'; 'diag': mean-field q(u), no C
     planes: int                 # Kzx digit planes of the int8 product (4 or 5), else 0
     p1: str                     # entry points: product 1, product 2, and the reduction of the partials to mean and var
     p2: str
@@ -763,8 +763,21 @@ def svgp_projection_plan(M, n, batch, dtype, first, second, i8_planes=4):
     plan, 16 in the float64-accumulating kernel (64-row tiles when its 128-row grid is under one round of the chip) -- so
     the buffer has T = max(T1, T2) rows and is ZERO-FILLED EXACTLY WHEN SOME ROW OF SOME PLANE IS WRITTEN BY NO KERNEL
     (T1 < T or T2 < T): finalize sums all T rows of all three planes, and no error code reports an uninitialised one.
-    'f64acc_t' (C accumulated in float64, float64 partials) follows a first product that can write float64 partials."""
+    'f64acc_t' (C accumulated in float64, float64 partials) follows a first product that can write float64 partials.
+    second = 'diag' (mean-field q(u) = N(m, diag(s^2)), every `first`): there is no second product.  p2 is the pass over A
+    that writes the float64 partials of q_j = sum_k (s_k^2 - 1) A_kj^2 -- T2 rows of a (batch, T2, n) buffer of their own --
+    and the partials buffer (2, batch, T, n) holds product 1's two planes only (T = T1: no row is left unwritten)."""
     f32 = dtype == torch.float32
+    if second == 'diag':
+        if first not in ('f32', 'f64acc', 'f64acc_b64', 'kzx_fused', 'i8', 'bf16') or (not f32 and (dtype, first) != (torch.float64, 'f32')) \
+                or (first == 'bf16' and M % 8):
+            raise BackendError(f'svgp_projection_plan: no {first} / diag projection of a {dtype} layer with M = {M}')
+        lib, sfx, pre = _lib.load(), 'f32' if f32 else 'f64', 'nsgp_svgp_tri_gemm_colstats_'
+        T1 = int(lib.nsgp_svgp_colstats_tiles(M, n, batch, 4 if f32 else 8) if first == 'f32' else lib.nsgp_i8_tiles(M)
+                 if first == 'i8' else lib.nsgp_svgp_bf16_tiles(M) if first == 'bf16' else lib.nsgp_svgp_f64acc_tiles_for(M, n, batch))
+        p1 = {'f32': pre + sfx, 'f64acc_b64': pre + 'f64acc_b64p32', 'kzx_fused': 'nsgp_svgp_kzx_gemm_colstats_f64acc'}.get(first, pre + first)
+        return ProjectionPlan(first, second, (5 if i8_planes == 5 else 4) if first == 'i8' else 0, p1, 'nsgp_svgp_diag_colsq_' + sfx,
+                              'nsgp_svgp_colstats_finalize_diag_' + sfx, T1, int(lib.nsgp_svgp_diag_tiles(M)), T1, dtype, False, False)
     if (not f32 and (dtype, first, second) != (torch.float64, 'f32', 'f32')) or (second == 'bf16' and M % 8) \
             or first not in ('f32', 'f64acc', 'f64acc_b64', 'kzx_fused', 'i8', 'bf16') or (first == 'bf16' and second != 'bf16') \
             or second not in ('f32', 'f64acc_t', 'bf16') or (second == 'f64acc_t' and first not in ('f64acc_b64', 'i8')):
@@ -793,9 +806,10 @@ def _run_projection(plan, dims, W, B, kin, Lq, m, base, base_add, affine, kzx_ou
     from or None), the bf16 cast / transpose, product 2 (Lq likewise) and finalize.  Returns A, C, mean, var."""
     (batch, M, n), dt, dev, st, T = dims, m.dtype, m.device, _stream(), plan.T
     flops = 1.0 * M * M * n * batch                      # 2 M M n / 2 (triangular operand)
+    diag = plan.second == 'diag'                         # mean-field q(u): Lq is s^2 - 1 (batch, M), there is no C
     A = torch.empty((batch, M, n), dtype=dt, device=dev)
-    C = torch.empty_like(A)
-    part = (torch.zeros if plan.zero else torch.empty)((3, batch, max(T, 1), n), dtype=plan.part_dtype, device=dev)
+    C = None if diag else torch.empty_like(A)
+    part = (torch.zeros if plan.zero else torch.empty)((2 if diag else 3, batch, max(T, 1), n), dtype=plan.part_dtype, device=dev)
     p0, p1 = _p(part[0]), _p(part[1])
     if kin is not None:
         kZ, kx, kls, kos = kin
@@ -822,7 +836,16 @@ def _run_projection(plan, dims, W, B, kin, Lq, m, base, base_add, affine, kzx_ou
         _lib.call('nsgp_cast_sq_bf16_f64' if W.dtype == torch.float64 else 'nsgp_cast_sq_bf16_f32', _p(W), _p(Wb), M, batch,
                   0, 1, st)
         _lib.call('nsgp_rbf_build_t_bf16', _p(kZ), _p(kx), _p(kls), _p(kos), batch, M, n, D, sx, _p(Kxz), st)
-        _timed(lambda: _lib.call(plan.p1, _p(Wb), 1, _p(Kxz), _p(m), batch, M, n, _p(A), _p(AT), p0, p1, st), flops, 'bf16')
+        _timed(lambda: _lib.call(plan.p1, _p(Wb), 1, _p(Kxz), _p(m), batch, M, n, _p(A), None if diag else _p(AT), p0, p1, st),
+               flops, 'bf16')
+    if diag:
+        mean, var = torch.empty((batch, n), dtype=dt, device=dev), torch.empty((batch, n), dtype=dt, device=dev)
+        x, sxb, Da, w, swb, c, scb = _affine_args(affine, batch, n, m)
+        pq = torch.empty((batch, max(plan.T2, 1), n), dtype=torch.float64, device=dev)
+        _lib.call(plan.p2, _p(A), _p(Lq), batch, M, n, _p(pq), plan.T2, st)
+        _lib.call(plan.fin, p0, T, _p(pq), plan.T2, _p(base), float(base_add), batch, n, _p(x), sxb, Da, _p(w), swb, _p(c), scb,
+                  _p(mean), _p(var), st)
+        return A, None, mean, var
     if plan.second == 'f32':
         _timed(lambda: _lib.call(plan.p2, _p(Lq), 1, _p(A), None, batch, M, n, _p(C), None, _p(part[2]), T, st), flops, dt)
     elif plan.second == 'f64acc_t':                      # C = Lq^T A accumulated in float64 (layers that feed the next layer)
@@ -965,6 +988,112 @@ def svgp_project_bwd(Lq, m, A, C, gmean, gvar, affine=None):
                              ws.numel() if ws is not None else 0, st), flops, ref.dtype)
     # accumulated onto a gradient that is already p.grad: nothing to hand to autograd for Lq
     return Abar, (None if lq_beta else Lqbar), mbar, basebar, wbar, cbar
+
+
+def svgp_project_diag(first, W, s2m1, m, base, base_add=0.0, affine=None, Kzx=None, Kzx64=None, kernel_inputs=None,
+                      W64f=None, i8_planes=4, i8_kzx_out=None):
+    """Forward projection of a layer with a mean-field q(u) = N(m, diag(s^2)): A = W Kzx in the arithmetic `first` names
+    (svgp_projection_plan; the operands of `svgp_project` / `svgp_project_bf16`: Kzx for 'f32' / 'f64acc', Kzx64 for
+    'f64acc_b64', kernel_inputs = (Z, x, ls, os) for 'kzx_fused' / 'i8' / 'bf16', W64f wherever the float64 W is read),
+    then ONE pass over A instead of the second product.  s2m1:(b,M) = s^2 - 1.
+    Returns A, mean = A^T m (+ the affine prior mean), var = base + base_add + sum_k s2m1_k A_kj^2, summed in float64."""
+    ref = _chk(W, s2m1, m, base, Kzx)
+    needs_w64 = first in ('f64acc', 'f64acc_b64', 'kzx_fused', 'i8')
+    if first not in ('f32', 'bf16') and not needs_w64:
+        raise BackendError(f'svgp_project_diag: unknown first product {first!r}')
+    if (needs_w64 and W64f is None) or (first in ('f32', 'f64acc')) != (Kzx is not None) \
+            or (first == 'f64acc_b64') != (Kzx64 is not None) or (first in ('kzx_fused', 'i8', 'bf16')) != (kernel_inputs is not None):
+        raise BackendError(f'svgp_project_diag: operands of a {first!r} first product')
+    kin = B = None
+    if kernel_inputs is not None:
+        kin, (batch, M, n) = _kernel_inputs_args(kernel_inputs, ref, 'svgp_project_diag')
+        if first == 'i8' and (ref.dtype != torch.float32 or kin[0].shape[2] > 4 or not _lib.load().nsgp_i8_supported(M)):
+            raise BackendError('svgp_project_diag: int8 product shapes (float32 layer, D <= 4, M <= 4096)')
+    else:
+        B = _c(Kzx64 if Kzx64 is not None else Kzx)
+        if B.dim() != 3 or B.device != ref.device or B.dtype != (torch.float64 if Kzx64 is not None else ref.dtype):
+            raise BackendError('svgp_project_diag: Kzx / Kzx64 must be (b,M,n) on the layer device')
+        batch, M, n = B.shape
+    W, s2m1, m, base = _c(W), _c(s2m1), _c(m), _c(base.reshape(-1))
+    if W.shape != (batch, M, M) or s2m1.shape != (batch, M) or m.shape != (batch, M) or base.shape != (batch,):
+        raise BackendError('svgp_project_diag: shapes')
+    if W64f is not None:
+        if ref.dtype != torch.float32 or W64f.dtype != torch.float64 or W64f.shape != (batch, M, M) or W64f.device != ref.device:
+            raise BackendError('svgp_project_diag: W64f must be the float64 (b,M,M) W of a float32 layer')
+        W = _c(W64f)
+    plan = svgp_projection_plan(M, n, batch, ref.dtype, first, 'diag', i8_planes)
+    if first == 'kzx_fused' and not svgp_kzx_fusable(W, kin[0], kin[1], n):
+        raise BackendError('svgp_project_diag: the generated-Kzx product needs whole tiles (svgp_kzx_fusable)')
+    A, _, mean, var = _run_projection(plan, (batch, M, n), W, B, kin, s2m1, m, base, base_add, affine, i8_kzx_out)
+    return A, mean, var
+
+
+def svgp_project_diag_bwd(m, s2m1, A, gmean, gvar, affine=None):
+    """Adjoints of svgp_project_diag: Abar = m gmean^T + 2 diag(s2m1) A diag(gvar) (the total adjoint of A), mbar = A gmean,
+    tbar = rowsum(A^2 diag(gvar)) (the gradient of s^2), from ONE pass over A; basebar = rowsum(gvar):(b,) and the gradients
+    (wbar, cbar) of the affine prior mean come from the rowdot launch, which reads no row of A here."""
+    ref = _chk(m, s2m1, A, gmean, gvar)
+    m, s2m1, A, gmean, gvar = _c(m), _c(s2m1), _c(A), _c(gmean), _c(gvar)
+    batch, M, n = A.shape
+    if m.shape != (batch, M) or s2m1.shape != (batch, M) or gmean.shape != (batch, n) or gvar.shape != (batch, n):
+        raise BackendError('svgp_project_diag_bwd: shapes')
+    sfx, st = _sfx(ref), _stream()
+    if A.numel() == 0:
+        raise BackendError('svgp_project_diag_bwd: empty A')
+    Abar, mbar, tbar = torch.empty_like(A), torch.empty_like(m), torch.empty_like(m)
+    basebar = torch.empty(batch, dtype=ref.dtype, device=ref.device)
+    wbar = cbar = None
+    x, sxb, D, w, swb, c, scb = _affine_args(affine, batch, n, ref)
+    shared = int(affine is not None and swb == 0 and scb == 0)
+    if affine is not None:
+        if w is not None and c is not None and batch > 1 and (swb == 0) != (scb == 0):
+            raise BackendError('affine prior mean: weights and constant must both be shared or both be per batch')
+        nb = 1 if shared else batch
+        if w is not None:
+            wbar = torch.empty((nb, D), dtype=ref.dtype, device=ref.device)
+        if c is not None:
+            cbar = torch.empty(nb, dtype=ref.dtype, device=ref.device)
+    ws = _ws(_lib.load().nsgp_svgp_diag_bwd_workspace(batch, M, n), ref.device)
+    _lib.call(f'nsgp_svgp_diag_bwd_{sfx}', _p(A), _p(m), _p(s2m1), _p(gmean), _p(gvar), batch, M, n, _p(Abar), _p(mbar),
+              _p(tbar), _p(ws), ws.numel(), st)
+    # the rows past M of rowdot_affine only (M = 0: basebar, wbar, cbar)
+    _lib.call(f'nsgp_rowdot_affine_{sfx}', _p(A), _p(gmean), _p(gvar), _p(x) if wbar is not None else None, sxb, D,
+              shared, batch, 0, n, _p(mbar), _p(basebar), _p(wbar), _p(cbar), st)
+    return Abar, mbar, tbar, basebar, wbar, cbar
+
+
+def _kl_meanfield_args(m, s2, what):
+    ref = _chk(m, s2)
+    m2, s2 = _c(m), _c(s2)
+    if m2.dim() == 1:
+        m2, s2 = m2.unsqueeze(0), s2.unsqueeze(0)
+    if m2.dim() != 2 or s2.shape != m2.shape or m2.numel() == 0:
+        raise BackendError(f'{what}: m, s2 must be (b,M) or (M,), not empty')
+    return ref, m2, s2
+
+
+def kl_meanfield_total(m, s2, scale=1.0, addin=None):
+    """1-element tensor  addin + scale * sum_b KL(N(m_b, diag(s2_b)) || N(0, I));  m, s2:(b,M) or (M,)."""
+    ref, m2, s2 = _kl_meanfield_args(m, s2, 'kl_meanfield_total')
+    if addin is not None:
+        _chk(ref, addin)
+        if addin.numel() != 1:
+            raise BackendError('kl_meanfield_total: addin must be a scalar')
+    out = torch.empty(1, dtype=ref.dtype, device=ref.device)
+    ws = _red_ws(ref)
+    _lib.call(f'nsgp_kl_meanfield_total_acc_fwd_{_sfx(ref)}', _p(m2), _p(s2), m2.shape[0], m2.shape[1], float(scale),
+              None if addin is None else _p(_c(addin).reshape(1)), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def kl_meanfield_total_bwd(m, s2, scale, gout):
+    """(gm, gs2) of kl_meanfield_total for the upstream gradient gout (a 1-element device tensor), in m's / s2's shapes."""
+    ref, m2, s22 = _kl_meanfield_args(m, s2, 'kl_meanfield_total_bwd')
+    _chk(ref, gout)
+    gm, gs2 = torch.empty_like(m2), torch.empty_like(s22)
+    _lib.call(f'nsgp_kl_meanfield_total_bwd_{_sfx(ref)}', _p(m2), _p(s22), m2.shape[0], m2.shape[1], float(scale),
+              _p(_c(gout).reshape(1)), _p(gm), _p(gs2), _stream())
+    return gm.reshape(m.shape), gs2.reshape(s2.shape)
 
 
 def dgp_sample(mean, var, eps):
@@ -1381,6 +1510,38 @@ class KlWhitenedTotalFn(torch.autograd.Function):
         _lib.call(f'nsgp_kl_whitened_total_bwd_{_sfx(m2)}', _p(m2), _p(L2), batch, M, ctx.scale, _p(_c(g).reshape(1)),
                   _p(gm), _p(gL), _stream())
         return gm.reshape(ctx.shapes[0]), gL.reshape(ctx.shapes[1]), None, (g if ctx.has_addin else None)
+
+
+class KlMeanFieldTotalFn(torch.autograd.Function):
+    """Scalar  addin + scale * sum_b KL(N(m_b, diag(s2_b)) || N(0, I))  -- KlWhitenedTotalFn for a mean-field q(u);
+    m, s2:(b,M) or (M,), s2 the variances.  backward reads the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, m, s2, scale, addin=None):
+        out = kl_meanfield_total(m, s2, scale, addin)
+        ctx.save_for_backward(m, s2)
+        ctx.scale, ctx.has_addin = float(scale), addin is not None
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        m, s2 = ctx.saved_tensors
+        gm, gs2 = kl_meanfield_total_bwd(m, s2, ctx.scale, g)
+        return gm, gs2, None, (g if ctx.has_addin else None)
+
+
+class KlMeanFieldFn(torch.autograd.Function):
+    """sum_b KL(N(m_b, diag(s2_b)) || N(0, I))   (whitened VariationalStrategy.kl_divergence of a mean-field q(u))."""
+
+    @staticmethod
+    def forward(ctx, m, s2):
+        ctx.save_for_backward(m, s2)
+        return kl_meanfield_total(m, s2).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        m, s2 = ctx.saved_tensors
+        return kl_meanfield_total_bwd(m, s2, 1.0, g)
 
 
 class DsviObjectiveFn(torch.autograd.Function):

@@ -162,7 +162,7 @@ def whiten(groups, jitter=1e-4, chol_bwd_f64=True, passthrough=False, out_dtype=
 
 
 def select_projection(dtype, M, D, n, kzx_f64, has_w64, fusable, forward_precision, whiten_matmul_f64, whiten_matmul_i8,
-                      fuse_kzx, hidden_var_f64):
+                      fuse_kzx, hidden_var_f64, diag_q=False):
     """Which arithmetic a layer's forward projection runs in, from sizes and the settings' values only: (first, second) in
     ops.svgp_projection_plan's names, the int8 product's Kzx planes, whether it takes the float64 W.  kzx_f64: the layer
     feeds the next one (settings.hidden_kzx_f64); has_w64: the float64 W of the whitening chain is at hand; fusable: the
@@ -180,7 +180,9 @@ def select_projection(dtype, M, D, n, kzx_f64, has_w64, fusable, forward_precisi
     next layer's inputs through sqrt(var) eps.  Measured after 1000 Adam steps at the headline shape (max-norm, vs the
     float64 oracle; tests/test_gpu_headline_precision.py): output mean 4.4e-6 with it, 5.2e-5 without (the reference's own
     float32 arithmetic: 4.5e-4); +0.12 ms on a 4.34 ms step.
-    'bf16' (BASELINE configs[4]; float32 layers, M % 8 == 0, else as 'f32'): C on the bf16 cores; 'bf16_all' also A."""
+    'bf16' (BASELINE configs[4]; float32 layers, M % 8 == 0, else as 'f32'): C on the bf16 cores; 'bf16_all' also A.
+    diag_q: q(u) is mean-field (SVGPMeanFieldLayerFn).  There is no C, so its rules do not apply and `second` is 'diag';
+    `first` and the planes are chosen as above."""
     fp = forward_precision
     w64 = dtype == torch.float32 and has_w64 and (whiten_matmul_f64 or fp == 'bf16_all')
     fuse = fp == 'f32' and fuse_kzx and w64 and fusable
@@ -190,7 +192,8 @@ def select_projection(dtype, M, D, n, kzx_f64, has_w64, fusable, forward_precisi
     bf16 = dtype == torch.float32 and fp in ('bf16', 'bf16_all') and M % 8 == 0
     first = 'bf16' if (bf16 and fp == 'bf16_all') else 'kzx_fused' if fuse else 'i8' if i8 else \
         'f64acc_b64' if can64 else 'f64acc' if w64 else 'f32'
-    return first, 'bf16' if bf16 else 'f64acc_t' if var64 else 'f32', 5 if (kzx_f64 and not bf16) else 4, bool(w64)
+    second = 'diag' if diag_q else 'bf16' if bf16 else 'f64acc_t' if var64 else 'f32'
+    return first, second, 5 if (kzx_f64 and not bf16) else 4, bool(w64)
 
 
 class SVGPLayerFn(torch.autograd.Function):
@@ -271,14 +274,87 @@ class SVGPLayerFn(torch.autograd.Function):
                 None if mean_c is None else cbar.reshape(mean_c.shape), None, None)
 
 
-def svgp_marginal(x, Z, ls, os_, m, Lq, jitter=1e-4, chol_bwd_f64=True, W64=None, mean_w=None, mean_c=None, W64f=None,
-                  kzx_f64=False):
+class SVGPMeanFieldLayerFn(torch.autograd.Function):
+    """(x, Z, ls, os, m, s2, W64, mean_w, mean_c) -> (mean:(b,n), var:(b,n)) for a mean-field q(u) = N(m, diag(s2)).
+
+    SVGPLayerFn with s2:(b,M), the variances of q(u), in place of Lq.  S = diag(s2) leaves ONE (M x M x n) product in the
+    forward pass (A = W Kzx, in whichever arithmetic select_projection names) and two in the backward:
+        var_j = os + 1e-4 + sum_k (s2_k - 1) A_kj^2             one pass over A, summed in float64
+        Abar  = m gmean^T + 2 diag(s2 - 1) A diag(gvar),  s2bar_k = sum_j A_kj^2 gvar_j,  mbar = A gmean     one pass over A
+        Kzxbar = W^T Abar,  Wbar = tril(Abar Kzx^T)             as in SVGPLayerFn
+    The Kzx handling is SVGPLayerFn's: the int8 build writes the float32 Kzx the backward needs, the generated-Kzx and
+    float64-Kzx forward passes leave it to the backward to build."""
+
+    @staticmethod
+    def forward(ctx, x, Z, ls, os_, m, s2, W64, mean_w, mean_c, W64f=None, kzx_f64=False):
+        from .gp import settings
+        W = W64 if W64.dtype == x.dtype else ops.cast(W64, x.dtype)
+        if W64f is None and W64.dtype == torch.float64 and x.dtype == torch.float32:
+            W64f = W64
+        first, _, planes, w64 = select_projection(
+            x.dtype, Z.shape[-2], Z.shape[-1], x.shape[-2], kzx_f64, W64f is not None,
+            settings.fuse_kzx.on() and ops.svgp_kzx_fusable(W64f, Z, x, x.shape[-2]), settings.forward_precision.value(),
+            settings.whiten_matmul_f64.on(), settings.whiten_matmul_i8.on(), settings.fuse_kzx.on(), settings.hidden_var_f64.value(),
+            diag_q=True)
+        W64f = W64f if w64 else None
+        affine = None if (mean_w is None and mean_c is None) else (x, mean_w, mean_c)
+        Kzx = Kzx64 = None
+        if first == 'f64acc_b64':
+            src = [x.detach(), Z.detach(), ls.detach(), os_.detach()]
+            dst = [torch.empty(t.shape, dtype=torch.float64, device=t.device) for t in src]
+            torch._foreach_copy_(dst, src)
+            Kzx64 = ops.rbf_build(dst[1], dst[0], dst[2], dst[3])
+        elif first in ('f32', 'f64acc'):
+            Kzx = ops.rbf_build(Z, x, ls, os_)           # (b,M,n)
+        kzx_out = [] if (first == 'i8' and any(ctx.needs_input_grad)) else None
+        s2m1 = s2.detach() - 1.0
+        A, mean, var = ops.svgp_project_diag(first, W, s2m1, m, os_, base_add=VAR_JITTER, affine=affine, Kzx=Kzx, Kzx64=Kzx64,
+                                             kernel_inputs=(Z, x, ls, os_) if first in ('kzx_fused', 'i8', 'bf16') else None,
+                                             W64f=W64f, i8_planes=planes, i8_kzx_out=kzx_out)
+        if kzx_out:
+            Kzx = kzx_out[0]
+        ctx.save_for_backward(x, Z, ls, os_, m, s2m1, W, Kzx, A, mean_w, mean_c)
+        ctx.w_dtype = W64.dtype
+        return mean, var
+
+    @staticmethod
+    def backward(ctx, gmean, gvar):
+        x, Z, ls, os_, m, s2m1, W, Kzx, A, mean_w, mean_c = ctx.saved_tensors
+        if Kzx is None:                                  # built here, once, for the Wbar product
+            Kzx = ops.rbf_build(Z, x, ls, os_)
+        gmean = gmean.contiguous()
+        affine = None if (mean_w is None and mean_c is None) else (x, mean_w, mean_c)
+        Abar, mbar, s2bar, basebar, wbar, cbar = ops.svgp_project_diag_bwd(m, s2m1, A, gmean, gvar.contiguous(), affine=affine)
+        Kzxbar = ops.gemm(W, Abar, ta=True, flags=GEMM_A_UPPER)                  # W^T Abar
+        Wbar = ops.gemm(Abar, Kzx, tb=True, flags=GEMM_C_LOWER)                  # tril(Abar Kzx^T)
+        need_x = ctx.needs_input_grad[0]
+        gZ, gx, gls, gos = ops.rbf_build_bwd(Z, x, ls, os_, Kzxbar, need_x1=True, need_x2=need_x)
+        gos = gos + basebar
+        if need_x:
+            if mean_w is not None:                       # d(prior mean)/dx = w  (deeper layers of a tied stack only)
+                gx = gx + gmean.unsqueeze(-1) * mean_w.reshape(-1, 1, x.shape[-1])
+            if x.dim() == 2:
+                gx = gx[0] if gx.shape[0] == 1 else gx.sum(0)
+        return (gx if need_x else None, gZ, gls.reshape(ls.shape), gos.reshape(os_.shape), mbar, s2bar,
+                Wbar if Wbar.dtype == ctx.w_dtype else ops.cast(Wbar, ctx.w_dtype),
+                None if mean_w is None else wbar.reshape(mean_w.shape),
+                None if mean_c is None else cbar.reshape(mean_c.shape), None, None)
+
+
+def svgp_marginal(x, Z, ls, os_, m, Lq=None, jitter=1e-4, chol_bwd_f64=True, W64=None, mean_w=None, mean_c=None, W64f=None,
+                  kzx_f64=False, s2=None):
     """mean and variance of q(f) at x for b whitened SVGPs; the mean excludes the prior mean function unless its
     affine parameters are passed (mean_w: LinearMean weights (D,) / (b,D), mean_c: constant or bias (1,) / (b,)).
+    q(u) = N(m, Lq Lq^T), or mean-field N(m, diag(s2)) when s2:(b,M) is given in place of Lq.
     Returns (mean, var, info); pass W64 (from `whiten`) to share one factorisation chain across layers."""
+    if (Lq is None) == (s2 is None):
+        raise ValueError('svgp_marginal: exactly one of Lq (Cholesky q(u)) and s2 (mean-field q(u)) expected')
     info = None
     if W64 is None:
         (W64,), info, ((Z, ls, os_),), (W64f,) = whiten([(Z, ls, os_)], jitter, chol_bwd_f64, passthrough=True,
                                                         out_dtype=x.dtype, with_f64=True)
-    mean, var = SVGPLayerFn.apply(x, Z, ls, os_, m, Lq, W64, mean_w, mean_c, W64f, kzx_f64)
+    if s2 is not None:
+        mean, var = SVGPMeanFieldLayerFn.apply(x, Z, ls, os_, m, s2, W64, mean_w, mean_c, W64f, kzx_f64)
+    else:
+        mean, var = SVGPLayerFn.apply(x, Z, ls, os_, m, Lq, W64, mean_w, mean_c, W64f, kzx_f64)
     return mean, var, info
