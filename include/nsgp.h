@@ -28,7 +28,7 @@ extern "C" {
 #define NSGP_MAX_DIM 8          /* input dimension D supported by the pairwise kernels */
 
 /* library / device identification (host) */
-int nsgp_abi_version(void);                 /* bumps when a signature changes */
+int nsgp_abi_version(void);                 /* bumps when a signature changes or an entry point goes; now 2 */
 const char* nsgp_build_arch(void);          /* "gfx950" */
 
 /* Measurement aid (bench.py's roofline context; no reference counterpart): the matrix-core rate THIS chip sustains.  A
@@ -514,16 +514,22 @@ int nsgp_dgp_sample_bwd_f64(const double* var, const double* eps, const double* 
                             int64_t n, int64_t b, double* gmean, double* gvar, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * K7  ELBO reductions.
- *   gauss_ell: out[s] = scale * sum_i -0.5*(((y_i-mu_si)^2 + v_si)/noise + log noise + log 2pi)
- *              (GaussianLikelihood.expected_log_prob summed over the minibatch, one value per sample
- *               s as VariationalELBO returns it; DeepApproximateMLL then averages over s --
- *               experiments/deepgp_spatial_bench.py:61,84-88); noise:(1) device.
- *              bwd: upstream gout:(S) on the DEVICE -> gmu, gv (S,n) and gnoise (1).
- *   kl_whitened: out[b] = 0.5*(||Lq_b||_F^2(lower) + m_b.m_b - M - 2 sum log|diag Lq_b|)
- *              (CholeskyVariationalDistribution vs N(0,I)); bwd writes gm, gLq (lower).
+ * K7  The DSVI objective: ELBO reductions.  Two terms,
+ *   gauss_ell:   sum_i -0.5*(((y_i-mu_si)^2 + v_si)/noise + log noise + log 2pi)   per likelihood sample s
+ *                (GaussianLikelihood.expected_log_prob summed over the minibatch); mu, v:(S,n), noise:(1) device
+ *   kl_whitened: 0.5*(||Lq_b||_F^2(lower) + m_b.m_b - M - 2 sum log|diag Lq_b|)   per batch element b
+ *                (CholeskyVariationalDistribution vs N(0,I)); only the lower triangle of Lq is read
+ *   kl_meanfield: 0.5 sum_k (s2_k + m_k^2 - 1 - log s2_k), its twin for q(u) = N(m, diag(s2)); m, s2:(batch,M)
+ * in three forms that run the same arithmetic per term (csrc/svgp.hip; DESIGN.md, "Objective terms"):
+ *   per term    one value per sample / batch element, as VariationalELBO and kl_divergence() return them
+ *   one scalar  (`total`) each term summed and scaled into ONE device scalar, chained through `addin`; the upstream
+ *               gradient of the backward is a 1-element DEVICE scalar (no host round trip)
+ *   fused       likelihood and every Cholesky layer's KL in one pair of launches
+ * ws: nsgp_reduce_workspace bytes unless stated.
  * ------------------------------------------------------------------------------------------ */
 size_t nsgp_reduce_workspace(int64_t n_elems, int elem_size);
+/* Per term.  gauss_ell_fwd: out[s] = scale * term_s.  bwd: upstream gout:(S) on the DEVICE -> gmu, gv (S,n) and gnoise (1,
+ * optional).  kl_whitened_fwd: out[b].  bwd: gm, gLq = gout (host scalar) * dKL; the strict upper triangle of gLq is zero. */
 int nsgp_gauss_ell_fwd_f32(const float* y, const float* mu, const float* v, const float* noise,
                            int64_t S, int64_t n, float scale, float* out, void* ws, size_t ws_bytes, void* stream);
 int nsgp_gauss_ell_bwd_f32(const float* y, const float* mu, const float* v, const float* noise,
@@ -534,19 +540,52 @@ int nsgp_gauss_ell_fwd_f64(const double* y, const double* mu, const double* v, c
 int nsgp_gauss_ell_bwd_f64(const double* y, const double* mu, const double* v, const double* noise,
                            int64_t S, int64_t n, double scale, const double* gout, double* gmu, double* gv, double* gnoise,
                            void* ws, size_t ws_bytes, void* stream);
-/* Scalar ("total") forms for the fused ELBO tail: one output, one device-resident upstream gradient.
- *   gauss_ell_total: out[0] = scale * sum_s sum_i E_q log N(y_i | f_si, noise)   (fold 1/S, 1/B, sign into scale);
- *       backward with gout a 1-element DEVICE scalar (no host round trip, no per-sample gradient vector)
- *   kl_whitened_total: out[0] = scale * sum_b KL(N(m_b, Lq_b Lq_b^T) || N(0, I));  backward: scale * gout[0] * dKL */
-/* The whole DSVI objective as one scalar -- DeepApproximateMLL(VariationalELBO(...)) of /root/reference/models/dgps.py's model,
- * driven at /root/reference/experiments/deepgp_spatial_bench.py:61,84-88 -- in TWO launches forward and TWO backward:
+int nsgp_kl_whitened_fwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float* out,
+                             void* ws, size_t ws_bytes, void* stream);
+int nsgp_kl_whitened_bwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float gout,
+                             float* gm, float* gLq, void* stream);
+int nsgp_kl_whitened_fwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double* out,
+                             void* ws, size_t ws_bytes, void* stream);
+int nsgp_kl_whitened_bwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double gout,
+                             double* gm, double* gLq, void* stream);
+/* One scalar.  gauss_ell_total: out[0] = scale * sum_s sum_i term_si (fold 1/S, 1/B and the sign into scale).
+ * kl_*_total_acc_fwd: out[0] = addin[0] + scale * sum_b KL_b, so the KL terms of several layers and the likelihood term chain
+ * into one scalar without separate additions (addin may be NULL; kl_whitened with addin given needs batch > 0;
+ * kl_meanfield with batch == 0 or M == 0 returns 0 without a launch and out is not written).
+ * *_total_bwd: gradients times scale * gout[0];  kl_meanfield: gm = scale gout[0] m, gs2 = scale gout[0] (1 - 1 / s2) / 2. */
+int nsgp_gauss_ell_total_fwd_f32(const float* y, const float* mu, const float* v, const float* noise, int64_t S,
+                                 int64_t n, float scale, float* out, void* ws, size_t ws_bytes, void* stream);
+int nsgp_gauss_ell_total_fwd_f64(const double* y, const double* mu, const double* v, const double* noise, int64_t S,
+                                 int64_t n, double scale, double* out, void* ws, size_t ws_bytes, void* stream);
+int nsgp_gauss_ell_total_bwd_f32(const float* y, const float* mu, const float* v, const float* noise, int64_t S,
+                                 int64_t n, float scale, const float* gout, float* gmu, float* gv, float* gnoise,
+                                 void* ws, size_t ws_bytes, void* stream);
+int nsgp_gauss_ell_total_bwd_f64(const double* y, const double* mu, const double* v, const double* noise, int64_t S,
+                                 int64_t n, double scale, const double* gout, double* gmu, double* gv, double* gnoise,
+                                 void* ws, size_t ws_bytes, void* stream);
+int nsgp_kl_whitened_total_acc_fwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float scale,
+                                       const float* addin, float* out, void* ws, size_t wsb, void* stream);
+int nsgp_kl_whitened_total_acc_fwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double scale,
+                                       const double* addin, double* out, void* ws, size_t wsb, void* stream);
+int nsgp_kl_whitened_total_bwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float scale,
+                                   const float* gout, float* gm, float* gLq, void* stream);
+int nsgp_kl_whitened_total_bwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double scale,
+                                   const double* gout, double* gm, double* gLq, void* stream);
+int nsgp_kl_meanfield_total_acc_fwd_f32(const float* m, const float* s2, int64_t batch, int64_t M, float scale,
+                                        const float* addin, float* out, void* ws, size_t wsb, void* stream);
+int nsgp_kl_meanfield_total_acc_fwd_f64(const double* m, const double* s2, int64_t batch, int64_t M, double scale,
+                                        const double* addin, double* out, void* ws, size_t wsb, void* stream);
+int nsgp_kl_meanfield_total_bwd_f32(const float* m, const float* s2, int64_t batch, int64_t M, float scale,
+                                    const float* gout, float* gm, float* gs2, void* stream);
+int nsgp_kl_meanfield_total_bwd_f64(const double* m, const double* s2, int64_t batch, int64_t M, double scale,
+                                    const double* gout, double* gm, double* gs2, void* stream);
+/* Fused: DeepApproximateMLL(VariationalELBO(...)) of models/dgps.py's model in TWO launches forward and TWO backward:
  *   out[0] = ell_scale * sum_s sum_i E_q log N(y_i | f_si, noise)
  *          + kl_scale  * sum_g sum_b KL(N(m_gb, Lq_gb Lq_gb^T) || N(0, I))           (fold 1/(B S), beta/num_data, signs into the scales)
  * mu, v:(S,n); `ngroups` <= 8 variational groups (one per layer: tied layers counted once) given as HOST arrays of device
- * pointers m[g]:(batch[g], M), Lq[g]:(batch[g], M, M) (lower triangle used) and host batch[g]; all groups share M.
+ * pointers m[g]:(batch[g], M), Lq[g]:(batch[g], M, M) and host batch[g]; all groups share M.
  * Backward: gout[0] (device) is the upstream gradient; writes gmu, gv:(S,n), gnoise[0] (optional), gm[g], gLq[g] (shapes of
- * m / Lq; the strict upper triangle of gLq is zero).  ws: nsgp_dsvi_objective_workspace bytes.  The per-term entry points
- * below stay for single-layer / non-whitened models. */
+ * m / Lq).  ws: nsgp_dsvi_objective_workspace bytes.  Mean-field layers and mixed M take the one-scalar chain. */
 size_t nsgp_dsvi_objective_workspace(int64_t S, int64_t n, int64_t M, int64_t total_batch, int elem_size);
 int nsgp_dsvi_objective_fwd_f32(const float* y, const float* mu, const float* v, const float* noise, int64_t S, int64_t n,
                                 float ell_scale, int ngroups, const void* const* m, const void* const* Lq,
@@ -564,50 +603,6 @@ int nsgp_dsvi_objective_bwd_f64(const double* y, const double* mu, const double*
                                 double ell_scale, int ngroups, const void* const* m, const void* const* Lq,
                                 const int64_t* batch, int64_t M, double kl_scale, const double* gout, double* gmu, double* gv,
                                 double* gnoise, void* const* gm, void* const* gLq, void* ws, size_t wsb, void* stream);
-int nsgp_gauss_ell_total_fwd_f32(const float* y, const float* mu, const float* v, const float* noise, int64_t S,
-                                 int64_t n, float scale, float* out, void* ws, size_t ws_bytes, void* stream);
-int nsgp_gauss_ell_total_fwd_f64(const double* y, const double* mu, const double* v, const double* noise, int64_t S,
-                                 int64_t n, double scale, double* out, void* ws, size_t ws_bytes, void* stream);
-int nsgp_gauss_ell_total_bwd_f32(const float* y, const float* mu, const float* v, const float* noise, int64_t S,
-                                 int64_t n, float scale, const float* gout, float* gmu, float* gv, float* gnoise,
-                                 void* ws, size_t ws_bytes, void* stream);
-int nsgp_gauss_ell_total_bwd_f64(const double* y, const double* mu, const double* v, const double* noise, int64_t S,
-                                 int64_t n, double scale, const double* gout, double* gmu, double* gv, double* gnoise,
-                                 void* ws, size_t ws_bytes, void* stream);
-int nsgp_kl_whitened_total_fwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float scale, float* out,
-                                   void* ws, size_t ws_bytes, void* stream);
-int nsgp_kl_whitened_total_fwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double scale,
-                                   double* out, void* ws, size_t ws_bytes, void* stream);
-/* out[0] = addin[0] + scale * sum_b KL_b: the KL terms of several layers (and the likelihood term) chain into ONE
- * scalar without separate additions (addin may be NULL; with addin given, batch must be > 0). */
-int nsgp_kl_whitened_total_acc_fwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float scale,
-                                       const float* addin, float* out, void* ws, size_t wsb, void* stream);
-int nsgp_kl_whitened_total_acc_fwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double scale,
-                                       const double* addin, double* out, void* ws, size_t wsb, void* stream);
-int nsgp_kl_whitened_total_bwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float scale,
-                                   const float* gout, float* gm, float* gLq, void* stream);
-int nsgp_kl_whitened_total_bwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double scale,
-                                   const double* gout, double* gm, double* gLq, void* stream);
-/* Mean-field twin: KL(N(m, diag(s2)) || N(0, I)) = 1/2 sum_k (s2_k + m_k^2 - 1 - log s2_k), m, s2:(batch, M).
- *   total_acc_fwd: out[0] = addin[0] + scale * sum_b KL_b (addin may be NULL; ws: nsgp_reduce_workspace bytes);
- *   total_bwd:     gm = scale gout[0] m,  gs2 = scale gout[0] (1 - 1 / s2) / 2,  gout a 1-element DEVICE scalar.
- * batch == 0 or M == 0: returns 0 without a launch (out is not written). */
-int nsgp_kl_meanfield_total_acc_fwd_f32(const float* m, const float* s2, int64_t batch, int64_t M, float scale,
-                                        const float* addin, float* out, void* ws, size_t wsb, void* stream);
-int nsgp_kl_meanfield_total_acc_fwd_f64(const double* m, const double* s2, int64_t batch, int64_t M, double scale,
-                                        const double* addin, double* out, void* ws, size_t wsb, void* stream);
-int nsgp_kl_meanfield_total_bwd_f32(const float* m, const float* s2, int64_t batch, int64_t M, float scale,
-                                    const float* gout, float* gm, float* gs2, void* stream);
-int nsgp_kl_meanfield_total_bwd_f64(const double* m, const double* s2, int64_t batch, int64_t M, double scale,
-                                    const double* gout, double* gm, double* gs2, void* stream);
-int nsgp_kl_whitened_fwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float* out,
-                             void* ws, size_t ws_bytes, void* stream);
-int nsgp_kl_whitened_bwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float gout,
-                             float* gm, float* gLq, void* stream);
-int nsgp_kl_whitened_fwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double* out,
-                             void* ws, size_t ws_bytes, void* stream);
-int nsgp_kl_whitened_bwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double gout,
-                             double* gm, double* gLq, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Small helpers on the same stream

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void mfma_rate_probe_kernel(int iters, unsigne
 
 extern "C" {
 
-int nsgp_abi_version(void) { return 1; }
+int nsgp_abi_version(void) { return 2; }
 const char* nsgp_build_arch(void) { return "gfx950"; }
 
 int nsgp_chol_bwd_phi_sym_f32(const float* P, float* S, int64_t n, int64_t ld, int64_t sP, int64_t batch,

@@ -283,8 +283,88 @@ __global__ void sample_bwd_kernel(const T* __restrict__ var, const T* __restrict
     gvar[q] = gv;
 }
 
-// ---- generic two-stage sum ---------------------------------------------------------------------
+// ---- the terms of the DSVI objective: every piece of arithmetic once -------------------------------------------------
+// The kernels further down are schedulers: each works out which (sample | group, batch element, chunk) a block owns and
+// calls a piece, so the per-term, the one-scalar and the fused entry points run the same text ("Objective
+// terms").  A piece is inlined with the contraction mode of THIS place (the default), whatever its caller sets.
 
+// sum of part[lo, hi) over one 256-thread workgroup (valid in thread 0; lds: 4 elements): second stage of every reduction
+template <typename T>
+__device__ __forceinline__ T part_sum(const T* __restrict__ part, int64_t lo, int64_t hi, T* lds) {
+    T s = T(0);
+    for (int64_t t = lo + threadIdx.x; t < hi; t += 256) s += part[t];
+    return block_sum_256(s, lds);
+}
+
+// one point of the Gaussian expected log-likelihood, d = y - mu, e = d^2 + v:  -1/2 (e / s2 + log s2 + log 2pi), or (GN)
+// its derivative with respect to the noise s2:  1/2 (e / s2^2 - 1 / s2)
+template <typename T, bool GN> __device__ __forceinline__ T gauss_term(T d, T v, T is2, T ls2) {
+    const T e = d * d + v;
+    if constexpr (GN) return T(0.5) * (e * is2 * is2 - is2);
+    else return T(-0.5) * (e * is2 + ls2 + T(1.8378770664093454835606594728112));
+}
+
+// this lane's sum of the term (gn: of its noise gradient) over points first, first + stride, ... < n of one sample row (mu,
+// v: that row).  gn selects per point: a caller that passes a constant gets the plain loop, and gauss_ell_part_kernel, which
+// passes its argument, keeps the select inside the loop -- and with it the un-contracted add it has always rounded with.
+template <typename T>
+__device__ __forceinline__ T gauss_row_sum(const T* __restrict__ y, const T* __restrict__ mu, const T* __restrict__ v,
+                                           const T* __restrict__ noise, int64_t first, int64_t stride, int64_t n, bool gn) {
+    const T s2 = noise[0];
+    const T is2 = T(1) / s2, ls2 = t_log(s2);
+    T acc = T(0);
+    for (int64_t i = first; i < n; i += stride) {
+        const T d = y[i] - mu[i];
+        acc += gn ? gauss_term<T, true>(d, v[i], is2, ls2) : gauss_term<T, false>(d, v[i], is2, ls2);
+    }
+    return acc;
+}
+
+// gmu, gv at element idx of (S, n) for the upstream factor coef (upstream gradient times the term's scale)
+template <typename T>
+__device__ __forceinline__ void gauss_adjoint_at(int64_t idx, const T* __restrict__ y, const T* __restrict__ mu,
+                                                 const T* __restrict__ noise, int64_t n, T coef, T* __restrict__ gmu,
+                                                 T* __restrict__ gv) {
+    const T is2 = T(1) / noise[0];
+    gmu[idx] = coef * (y[idx % n] - mu[idx]) * is2;
+    gv[idx] = T(-0.5) * coef * is2;
+}
+
+// this lane's share of  sum_{j <= i} l_ij^2 + sum_i (m_i^2 - 2 log |l_ii|)  (twice KL(N(m, L L^T) || N(0, I)), plus M) over
+// rows xb, xb + nblk, ... of one (m, L); only the lower triangle is read (no 64-bit div/mod per element)
+template <typename T>
+__device__ __forceinline__ T kl_rows_sum(const T* __restrict__ m, const T* __restrict__ L, int64_t M, int64_t xb,
+                                         int64_t nblk) {
+    T acc = T(0);
+    for (int64_t i = xb; i < M; i += nblk) {
+        const T* row = L + i * M;
+        for (int64_t j = threadIdx.x; j <= i; j += 256) {
+            const T l = row[j];
+            acc += l * l;
+            if (j == i) acc += m[i] * m[i] - T(2) * t_log(l < T(0) ? -l : l);
+        }
+    }
+    return acc;
+}
+
+// gLq at element idx of one (batch, M, M) group (zero above the diagonal), and gm beside each diagonal element, for the
+// upstream factor go
+template <typename T>
+__device__ __forceinline__ void kl_adjoint_at(int64_t idx, const T* __restrict__ m, const T* __restrict__ Lq, int64_t M, T go,
+                                              T* __restrict__ gm, T* __restrict__ gLq) {
+    const int64_t e = idx % (M * M), b = idx / (M * M);
+    const int64_t i = e / M, j = e % M;
+    T g = T(0);
+    if (j <= i) {
+        const T l = Lq[idx];
+        g = go * (i == j ? l - T(1) / l : l);
+        if (i == j) gm[b * M + i] = go * m[b * M + i];
+    }
+    gLq[idx] = g;
+}
+
+// ---- per-term kernels --------------------------------------------------------------------------------------------------
+// out[o] = scale * sum(part[o nparts .. (o + 1) nparts)) + add (+ add_dev[o])
 template <typename T>
 __global__ __launch_bounds__(256) void reduce_final_kernel(const T* __restrict__ part, int64_t nparts, int64_t nout,
                                                            T scale, T add, T* __restrict__ out,
@@ -292,15 +372,12 @@ __global__ __launch_bounds__(256) void reduce_final_kernel(const T* __restrict__
     __shared__ T lds[4];
     const int64_t o = blockIdx.x;
     if (o >= nout) return;
-    T s = T(0);
-    for (int64_t t = threadIdx.x; t < nparts; t += 256) s += part[o * nparts + t];
-    s = block_sum_256(s, lds);
+    const T s = part_sum(part, o * nparts, (o + 1) * nparts, lds);
     if (threadIdx.x == 0) out[o] = scale * s + add + (add_dev ? add_dev[o] : T(0));
 }
 
-// ---- gaussian expected log-likelihood (per sample row s) -------------------------------------------
-// part[s * gridDim.x + blk] = (gout ? gout[s * gs] : 1) * sum over a chunk of row s of      (gs = 0: one shared gout)
-//     want_gnoise ? 1/2 (e/s2^2 - 1/s2) : -1/2 (e/s2 + log s2 + log 2pi),  e = (y - mu)^2 + v
+// part[s * gridDim.x + blk] = (gout ? gout[s * gs] : 1) * sum over block blk's chunk of sample row s of the Gaussian term, or
+// (want_gnoise) of its noise gradient                                                       (gs = 0: one shared gout)
 template <typename T>
 __global__ __launch_bounds__(256) void gauss_ell_part_kernel(const T* __restrict__ y, const T* __restrict__ mu,
                                                              const T* __restrict__ v, const T* __restrict__ noise,
@@ -308,15 +385,8 @@ __global__ __launch_bounds__(256) void gauss_ell_part_kernel(const T* __restrict
                                                              int want_gnoise, T* __restrict__ part) {
     __shared__ T lds[4];
     const int64_t s = blockIdx.y;
-    const T s2 = noise[0];
-    const T is2 = T(1) / s2, ls2 = t_log(s2);
-    const T l2pi = T(1.8378770664093454835606594728112);
-    T acc = T(0);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const T d = y[i] - mu[s * n + i];
-        const T e = d * d + v[s * n + i];
-        acc += want_gnoise ? T(0.5) * (e * is2 * is2 - is2) : T(-0.5) * (e * is2 + ls2 + l2pi);
-    }
+    T acc = gauss_row_sum(y, mu + s * n, v + s * n, noise, (int64_t)blockIdx.x * 256 + threadIdx.x,
+                          (int64_t)gridDim.x * 256, n, want_gnoise != 0);
     acc = block_sum_256(acc, lds);
     if (threadIdx.x == 0) part[s * gridDim.x + blockIdx.x] = gout ? gout[s * gs] * acc : acc;
 }
@@ -326,30 +396,16 @@ __global__ void gauss_ell_bwd_kernel(const T* __restrict__ y, const T* __restric
                                      const T* __restrict__ gout, int64_t gs, int64_t S, int64_t n, T scale,
                                      T* __restrict__ gmu, T* __restrict__ gv) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= S * n) return;
-    const T is2 = T(1) / noise[0];
-    const T coef = gout[(idx / n) * gs] * scale;
-    gmu[idx] = coef * (y[idx % n] - mu[idx]) * is2;
-    gv[idx] = T(-0.5) * coef * is2;
+    if (idx < S * n) gauss_adjoint_at(idx, y, mu, noise, n, gout[(idx / n) * gs] * scale, gmu, gv);
 }
 
-// ---- KL(q(u) || N(0, I)) --------------------------------------------------------------------------
+// part[b * gridDim.x + blk] = block blk's rows of batch element b
 template <typename T>
 __global__ __launch_bounds__(256) void kl_part_kernel(const T* __restrict__ m, const T* __restrict__ Lq, int64_t M,
                                                       T* __restrict__ part) {
     __shared__ T lds[4];
     const int64_t b = blockIdx.y;
-    const T* L = Lq + b * M * M;
-    T acc = T(0);
-    // rows blockIdx.x, blockIdx.x + gridDim.x, ...; only the lower triangle is read (no 64-bit div/mod per element)
-    for (int64_t i = blockIdx.x; i < M; i += gridDim.x) {
-        const T* row = L + i * M;
-        for (int64_t j = threadIdx.x; j <= i; j += 256) {
-            const T l = row[j];
-            acc += l * l;
-            if (j == i) acc += m[b * M + i] * m[b * M + i] - T(2) * t_log(l < T(0) ? -l : l);
-        }
-    }
+    T acc = kl_rows_sum(m + b * M, Lq + b * M * M, M, (int64_t)blockIdx.x, (int64_t)gridDim.x);
     acc = block_sum_256(acc, lds);
     if (threadIdx.x == 0) part[b * gridDim.x + blockIdx.x] = acc;
 }
@@ -360,15 +416,7 @@ __global__ void kl_bwd_kernel(const T* __restrict__ m, const T* __restrict__ Lq,
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= batch * M * M) return;
     if (gdev) gout *= gdev[0];                          // upstream gradient read on the device (no host scalar)
-    const int64_t e = idx % (M * M), b = idx / (M * M);
-    const int64_t i = e / M, j = e % M;
-    T g = T(0);
-    if (j <= i) {
-        const T l = Lq[idx];
-        g = gout * (i == j ? l - T(1) / l : l);
-        if (i == j) gm[b * M + i] = gout * m[b * M + i];
-    }
-    gLq[idx] = g;
+    kl_adjoint_at(idx, m, Lq, M, gout, gm, gLq);
 }
 
 template <typename T>
@@ -419,12 +467,17 @@ int sample_bwd_impl(const T* var, const T* eps, const T* gh, int64_t S, int64_t 
     return nsgp_launch_status();
 }
 
+// blocks of partial sums: per sample row of the likelihood (each strides over the row by nblk * 256), per batch element of
+// the whitened KL (rows stride by nblk), and over all tot = batch * M > 0 elements of the mean-field KL
 static inline int64_t gauss_blocks(int64_t n) {
-    int64_t nblk = cdiv64(n, 1024);
-    if (nblk > 64) nblk = 64;
-    if (nblk < 1) nblk = 1;
+    int64_t nblk = cdiv64(n, 1024); if (nblk > 64) nblk = 64; if (nblk < 1) nblk = 1;
     return nblk;
 }
+static inline int64_t kl_blocks(int64_t M) {
+    int64_t nblk = cdiv64(M * M, 1024); if (nblk > 256) nblk = 256; if (nblk < 1) nblk = 1;
+    return nblk;
+}
+static inline int64_t kl_diag_blocks(int64_t tot) { return cdiv64(tot, 1024) > 256 ? 256 : cdiv64(tot, 1024); }
 
 // `total`: out[0] = scale * sum over ALL samples and points (the caller folds 1/S into scale), one launch less
 // downstream than an (S,) vector followed by a mean; the backward then takes ONE upstream gradient gout[0].
@@ -439,12 +492,9 @@ int gauss_fwd_impl(const T* y, const T* mu, const T* v, const T* noise, int64_t 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL((gauss_ell_part_kernel<T>), dim3((unsigned)nblk, (unsigned)S), dim3(256), 0, st, y, mu, v, noise,
                        (const T*)nullptr, (int64_t)0, n, 0, (T*)ws);
-    if (total)
-        hipLaunchKernelGGL((reduce_final_kernel<T>), dim3(1), dim3(256), 0, st, (const T*)ws, S * nblk, (int64_t)1, scale,
-                           T(0), out);
-    else
-        hipLaunchKernelGGL((reduce_final_kernel<T>), dim3((unsigned)S), dim3(256), 0, st, (const T*)ws, nblk, S, scale,
-                           T(0), out);
+    const int64_t nout = total ? 1 : S;                  // one sum of all S nblk partials, or S sums of nblk
+    hipLaunchKernelGGL((reduce_final_kernel<T>), dim3((unsigned)nout), dim3(256), 0, st, (const T*)ws, S * nblk / nout, nout,
+                       scale, T(0), out);
     return nsgp_launch_status();
 }
 
@@ -477,16 +527,13 @@ int kl_fwd_impl(const T* m, const T* Lq, int64_t batch, int64_t M, T* out, void*
                 bool total = false, T scale = T(1), const T* addin = nullptr) {
     if (!m) return -1; if (!Lq) return -2; if (batch < 0) return -3; if (M < 0) return -4; if (!out) return -5;
     if (batch == 0) return 0;
-    int64_t nblk = cdiv64(M * M, 1024); if (nblk > 256) nblk = 256; if (nblk < 1) nblk = 1;
+    const int64_t nblk = kl_blocks(M);
     if (!ws || wsb < (size_t)(batch * nblk) * sizeof(T)) return -6;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL((kl_part_kernel<T>), dim3((unsigned)nblk, (unsigned)batch), dim3(256), 0, st, m, Lq, M, (T*)ws);
-    if (total)                                           // out[0] = scale * sum_b KL_b
-        hipLaunchKernelGGL((reduce_final_kernel<T>), dim3(1), dim3(256), 0, st, (const T*)ws, batch * nblk, (int64_t)1,
-                           T(0.5) * scale, T(-0.5) * T(M) * T(batch) * scale, out, addin);
-    else
-        hipLaunchKernelGGL((reduce_final_kernel<T>), dim3((unsigned)batch), dim3(256), 0, st, (const T*)ws, nblk, batch,
-                           T(0.5), T(-0.5) * T(M), out);
+    const int64_t nout = total ? 1 : batch;              // total: out[0] = addin[0] + scale * sum_b KL_b; else scale is 1
+    hipLaunchKernelGGL((reduce_final_kernel<T>), dim3((unsigned)nout), dim3(256), 0, st, (const T*)ws, batch * nblk / nout,
+                       nout, T(0.5) * scale, T(-0.5) * T(M) * T(batch / nout) * scale, out, addin);
     return nsgp_launch_status();
 }
 
@@ -517,13 +564,15 @@ template <typename T> struct ObjGroups {
     int ng;
 };
 
-static inline int64_t kl_blocks(int64_t M) {
-    int64_t nblk = cdiv64(M * M, 1024); if (nblk > 256) nblk = 256; if (nblk < 1) nblk = 1;
-    return nblk;
+// the group g that block kb of a grid's KL region belongs to
+template <typename T> __device__ __forceinline__ int obj_group_of(const ObjGroups<T>& G, int kb) {
+    int g = 0;
+    while (g + 1 < G.ng && kb >= G.blk0[g + 1]) ++g;
+    return g;
 }
 
-// blocks [0, S nblk_e): likelihood partials (block (s, x) strides over row s); then, per group and batch element, nblk_k
-// blocks of KL partials (rows x, x + nblk_k, ... of the lower triangle): the arithmetic of gauss_ell_part / kl_part
+// blocks [0, S nblk_e): likelihood partials (block (s, x) strides over row s, as gauss_ell_part_kernel's); then, per group
+// and batch element, nblk_k blocks of KL partials (rows x, x + nblk_k, ... as kl_part_kernel's)
 template <typename T>
 __global__ __launch_bounds__(256) void dsvi_obj_part_kernel(const T* __restrict__ y, const T* __restrict__ mu,
                                                             const T* __restrict__ v, const T* __restrict__ noise, int64_t n,
@@ -531,32 +580,15 @@ __global__ __launch_bounds__(256) void dsvi_obj_part_kernel(const T* __restrict_
                                                             T* __restrict__ part) {
     __shared__ T lds[4];
     const int b = (int)blockIdx.x;
-    T acc = T(0);
+    T acc;
     if (b < n_ell) {
         const int64_t s = b / nblk_e, xb = b % nblk_e;
-        const T s2 = noise[0];
-        const T is2 = T(1) / s2, ls2 = t_log(s2);
-        const T l2pi = T(1.8378770664093454835606594728112);
-        for (int64_t i = xb * 256 + threadIdx.x; i < n; i += (int64_t)nblk_e * 256) {
-            const T d = y[i] - mu[s * n + i];
-            acc += T(-0.5) * ((d * d + v[s * n + i]) * is2 + ls2 + l2pi);
-        }
+        acc = gauss_row_sum(y, mu + s * n, v + s * n, noise, xb * 256 + threadIdx.x, (int64_t)nblk_e * 256, n, false);
     } else {
-        const int kb = b - n_ell;
-        int g = 0;
-        while (g + 1 < G.ng && kb >= G.blk0[g + 1]) ++g;
+        const int kb = b - n_ell, g = obj_group_of(G, kb);
         const int rel = kb - G.blk0[g];
         const int64_t bi = rel / nblk_k, xb = rel % nblk_k;
-        const T* L = G.Lq[g] + bi * M * M;
-        const T* mm = G.m[g] + bi * M;
-        for (int64_t i = xb; i < M; i += nblk_k) {
-            const T* row = L + i * M;
-            for (int64_t j = threadIdx.x; j <= i; j += 256) {
-                const T l = row[j];
-                acc += l * l;
-                if (j == i) acc += mm[i] * mm[i] - T(2) * t_log(l < T(0) ? -l : l);
-            }
-        }
+        acc = kl_rows_sum(G.m[g] + bi * M, G.Lq[g] + bi * M * M, M, xb, (int64_t)nblk_k);
     }
     acc = block_sum_256(acc, lds);
     if (threadIdx.x == 0) part[b] = acc;
@@ -567,12 +599,9 @@ template <typename T>
 __global__ __launch_bounds__(256) void dsvi_obj_final_kernel(const T* __restrict__ part, int n_ell, int n_all, T ell_scale,
                                                              T kl_scale, T kl_half_const, T* __restrict__ out) {
     __shared__ T lds[4];
-    T a = T(0), k = T(0);
-    for (int t = threadIdx.x; t < n_ell; t += 256) a += part[t];
-    for (int t = n_ell + threadIdx.x; t < n_all; t += 256) k += part[t];
-    a = block_sum_256(a, lds);
+    const T a = part_sum(part, (int64_t)0, (int64_t)n_ell, lds);
     __syncthreads();
-    k = block_sum_256(k, lds);
+    const T k = part_sum(part, (int64_t)n_ell, (int64_t)n_all, lds);
     if (threadIdx.x == 0) out[0] = ell_scale * a + kl_scale * (T(0.5) * k - kl_half_const);
 }
 
@@ -589,40 +618,18 @@ __global__ __launch_bounds__(256) void dsvi_obj_bwd_kernel(const T* __restrict__
     const T up = gout[0];
     if (b < nb_e) {
         const int64_t idx = (int64_t)b * 256 + threadIdx.x;
-        if (idx >= S * n) return;
-        const T is2 = T(1) / noise[0];
-        const T coef = up * ell_scale;
-        gmu[idx] = coef * (y[idx % n] - mu[idx]) * is2;
-        gv[idx] = T(-0.5) * coef * is2;
+        if (idx < S * n) gauss_adjoint_at(idx, y, mu, noise, n, up * ell_scale, gmu, gv);
         return;
     }
     if (b < nb_e + nb_kl) {
-        const int kb = b - nb_e;
-        int g = 0;
-        while (g + 1 < G.ng && kb >= G.blk0[g + 1]) ++g;
+        const int kb = b - nb_e, g = obj_group_of(G, kb);
         const int64_t idx = (int64_t)(kb - G.blk0[g]) * 256 + threadIdx.x;
-        if (idx >= (int64_t)G.batch[g] * M * M) return;
-        const int64_t e = idx % (M * M), bi = idx / (M * M);
-        const int64_t i = e / M, j = e % M;
-        const T go = up * kl_scale;
-        T gg = T(0);
-        if (j <= i) {
-            const T l = G.Lq[g][idx];
-            gg = go * (i == j ? l - T(1) / l : l);
-            if (i == j) G.gm[g][bi * M + i] = go * G.m[g][bi * M + i];
-        }
-        G.gLq[g][idx] = gg;
+        if (idx < (int64_t)G.batch[g] * M * M) kl_adjoint_at(idx, G.m[g], G.Lq[g], M, up * kl_scale, G.gm[g], G.gLq[g]);
         return;
     }
-    // noise-gradient partials: d/d noise of -1/2 (e / s2 + log s2) = 1/2 (e / s2^2 - 1 / s2)
     const int rb = b - nb_e - nb_kl;
     const int64_t s = rb / nblk_e, xb = rb % nblk_e;
-    const T is2 = T(1) / noise[0];
-    T acc = T(0);
-    for (int64_t i = xb * 256 + threadIdx.x; i < n; i += (int64_t)nblk_e * 256) {
-        const T d = y[i] - mu[s * n + i];
-        acc += T(0.5) * ((d * d + v[s * n + i]) * is2 * is2 - is2);
-    }
+    T acc = gauss_row_sum(y, mu + s * n, v + s * n, noise, xb * 256 + threadIdx.x, (int64_t)nblk_e * 256, n, true);
     acc = block_sum_256(acc, lds);
     if (threadIdx.x == 0) part_gn[rb] = acc;
 }
@@ -631,9 +638,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void dsvi_obj_gnoise_kernel(const T* __restrict__ part, int nparts, T ell_scale,
                                                               const T* __restrict__ gout, T* __restrict__ gnoise) {
     __shared__ T lds[4];
-    T a = T(0);
-    for (int t = threadIdx.x; t < nparts; t += 256) a += part[t];
-    a = block_sum_256(a, lds);
+    const T a = part_sum(part, (int64_t)0, (int64_t)nparts, lds);
     if (threadIdx.x == 0) gnoise[0] = gout[0] * ell_scale * a;
 }
 
@@ -858,9 +863,7 @@ __global__ __launch_bounds__(256) void kl_diag_final_kernel(const T* __restrict_
                                                             const T* __restrict__ addin, T* __restrict__ out) {
 #pragma clang fp contract(off)
     __shared__ T lds[4];
-    T s = T(0);
-    for (int64_t t = threadIdx.x; t < nparts; t += 256) s += part[t];
-    s = block_sum_256(s, lds);
+    const T s = part_sum(part, (int64_t)0, nparts, lds);
     if (threadIdx.x == 0) {
         const T r = scale * s;
         out[0] = addin ? addin[0] + r : r;
@@ -947,7 +950,7 @@ static int kl_diag_fwd_impl(const T* m, const T* s2, int64_t batch, int64_t M, T
                             size_t wsb, void* stream) {
     if (!m) return -1; if (!s2) return -2; if (batch < 0) return -3; if (M < 0) return -4; if (!out) return -7;
     if (batch == 0 || M == 0) return 0;
-    int64_t nblk = cdiv64(batch * M, 1024); if (nblk > 256) nblk = 256;
+    const int64_t nblk = kl_diag_blocks(batch * M);
     if (!ws) return -8; if (wsb < (size_t)nblk * sizeof(T)) return -9;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL((kl_diag_part_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, st, m, s2, batch * M, (T*)ws);
@@ -1075,7 +1078,6 @@ int nsgp_kl_whitened_bwd_f64(const double* m, const double* Lq, int64_t batch, i
                              double* gLq, void* stream) {
     return kl_bwd_impl<double>(m, Lq, batch, M, gout, gm, gLq, stream);
 }
-
 
 int nsgp_svgp_colstats_finalize_f32(const float* part_dot, const float* part_sq_a, const float* part_sq_c,
                                     const float* base, int64_t batch, int64_t tiles, int64_t n, float* mean,
@@ -1225,14 +1227,6 @@ int nsgp_gauss_ell_total_bwd_f64(const double* y, const double* mu, const double
                                  int64_t n, double scale, const double* gout, double* gmu, double* gv, double* gnoise,
                                  void* ws, size_t wsb, void* stream) {
     return gauss_bwd_impl<double>(y, mu, v, noise, S, n, scale, gout, gmu, gv, gnoise, ws, wsb, stream, true);
-}
-int nsgp_kl_whitened_total_fwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float scale, float* out,
-                                   void* ws, size_t wsb, void* stream) {
-    return kl_fwd_impl<float>(m, Lq, batch, M, out, ws, wsb, stream, true, scale);
-}
-int nsgp_kl_whitened_total_fwd_f64(const double* m, const double* Lq, int64_t batch, int64_t M, double scale,
-                                   double* out, void* ws, size_t wsb, void* stream) {
-    return kl_fwd_impl<double>(m, Lq, batch, M, out, ws, wsb, stream, true, scale);
 }
 int nsgp_kl_whitened_total_acc_fwd_f32(const float* m, const float* Lq, int64_t batch, int64_t M, float scale,
                                        const float* addin, float* out, void* ws, size_t wsb, void* stream) {

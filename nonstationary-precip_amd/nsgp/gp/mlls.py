@@ -113,36 +113,30 @@ def fused_dsvi_objective(base, approximate_dist_f, target, ell_scale, kl_scale, 
     strategies = getattr(base.model.variational_strategy, 'sub_variational_strategies', None)
     if strategies is None or any(True for _ in base.model.added_loss_terms()) or any(True for _ in base.named_priors()):
         return None
-    pairs, mean_field = [], False
+    layers = []                                          # (kind, (mean, the kind's second operand)) per layer
     for st in strategies:
         vd = getattr(st, '_variational_distribution', None)
         if vd is None or not hasattr(st, 'whiten_group'):
             return None
         if hasattr(vd, '_variational_stddev'):           # mean-field q(u): its KL node takes the variances s^2
-            mean_field = True
-            pairs.append((vd.variational_mean, None, vd))
+            layers.append(('mean_field', (vd.variational_mean, vd)))
         elif hasattr(vd, 'chol_variational_covar'):
-            pairs.append((vd.variational_mean, vd.chol_variational_covar, None))
+            layers.append(('cholesky', (vd.variational_mean, vd.chol_variational_covar)))
         else:
             return None
     sign = -1.0 if negate else 1.0                       # negate: the loss -ELBO itself, no separate negation
-    if mean_field:                                       # the chain: one KL-total node per layer, of the layer's own kind
-        total = ops.GaussEllTotalFn.apply(target, mean, var, lik.noise, sign * float(ell_scale))
-        for m, Lq, vd in pairs:
-            if vd is None:
-                total = ops.KlWhitenedTotalFn.apply(m, Lq, -sign * float(kl_scale), total)
-            else:
-                total = ops.KlMeanFieldTotalFn.apply(m, vd.variational_stddev.square(), -sign * float(kl_scale), total)
-        return total
-    pairs = [(m, Lq) for m, Lq, _ in pairs]
-    Ms = {Lq.shape[-1] for _, Lq in pairs}
-    if pairs and len(Ms) == 1 and len(pairs) <= 8 and all(m.dtype == mean.dtype for m, _ in pairs):
+    ell, kl = sign * float(ell_scale), -sign * float(kl_scale)
+    chol = [pair for kind, pair in layers if kind == 'cholesky']
+    if layers and len(chol) == len(layers) <= 8 and len({Lq.shape[-1] for _, Lq in chol}) == 1 \
+            and all(m.dtype == mean.dtype for m, _ in chol):
         # every layer's KL and the likelihood term in one pair of launches (nsgp_dsvi_objective_fwd / _bwd)
-        flat = [t for pr in pairs for t in pr]
-        return ops.DsviObjectiveFn.apply(target, mean, var, lik.noise, sign * float(ell_scale), -sign * float(kl_scale), *flat)
-    total = ops.GaussEllTotalFn.apply(target, mean, var, lik.noise, sign * float(ell_scale))
-    for m, Lq in pairs:                                  # each KL term is added into the running scalar by its own kernel
-        total = ops.KlWhitenedTotalFn.apply(m, Lq, -sign * float(kl_scale), total)
+        return ops.DsviObjectiveFn.apply(target, mean, var, lik.noise, ell, kl, *[t for pair in chol for t in pair])
+    total = ops.GaussEllTotalFn.apply(target, mean, var, lik.noise, ell)
+    for kind, (m, q) in layers:                          # the chain: each layer's KL node, of the layer's own kind, adds its
+        if kind == 'cholesky':                           # term into the running scalar
+            total = ops.KlWhitenedTotalFn.apply(m, q, kl, total)
+        else:
+            total = ops.KlMeanFieldTotalFn.apply(m, q.variational_stddev.square(), kl, total)
     return total
 
 

@@ -207,7 +207,7 @@ class VariationalStrategy(_VariationalStrategy):
         """KL(q(u) || N(0, I)) summed over the batch; q(u) = N(m, Lq Lq^T) or mean-field N(m, diag(s^2))."""
         m = self._variational_distribution.variational_mean
         if self._mean_field:
-            return ops.KlMeanFieldFn.apply(m, self._variational_distribution.variational_stddev.square())
+            return ops.KlMeanFieldTotalFn.apply(m, self._variational_distribution.variational_stddev.square(), 1.0)
         Lq = self._variational_distribution.chol_variational_covar
         return ops.KlWhitenedFn.apply(m, Lq)
 

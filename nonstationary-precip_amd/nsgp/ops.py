@@ -1075,14 +1075,10 @@ def _kl_meanfield_args(m, s2, what):
 def kl_meanfield_total(m, s2, scale=1.0, addin=None):
     """1-element tensor  addin + scale * sum_b KL(N(m_b, diag(s2_b)) || N(0, I));  m, s2:(b,M) or (M,)."""
     ref, m2, s2 = _kl_meanfield_args(m, s2, 'kl_meanfield_total')
-    if addin is not None:
-        _chk(ref, addin)
-        if addin.numel() != 1:
-            raise BackendError('kl_meanfield_total: addin must be a scalar')
     out = torch.empty(1, dtype=ref.dtype, device=ref.device)
     ws = _red_ws(ref)
     _lib.call(f'nsgp_kl_meanfield_total_acc_fwd_{_sfx(ref)}', _p(m2), _p(s2), m2.shape[0], m2.shape[1], float(scale),
-              None if addin is None else _p(_c(addin).reshape(1)), _p(out), _p(ws), ws.numel(), _stream())
+              _addin_arg(ref, addin, 'kl_meanfield_total'), _p(out), _p(ws), ws.numel(), _stream())
     return out
 
 
@@ -1124,58 +1120,113 @@ def _red_ws(ref):
     return _ws(_lib.load().nsgp_reduce_workspace(0, ref.element_size()), ref.device)
 
 
-def gauss_ell(y, mu, v, noise, scale):
-    """out[s] = scale * sum_i E_q log N(y_i | f_si, noise);  mu, v:(S,n)  y:(n,)  noise: 1-element tensor."""
+def _gauss_args(y, mu, v, noise, what):
     ref = _chk(y, mu, v, noise)
     y, mu, v = _c(y), _c(mu), _c(v)
+    if mu.dim() != 2 or y.shape != (mu.shape[1],) or v.shape != mu.shape:
+        raise BackendError(f'{what}: shapes')
+    return ref, y, mu, v, noise.reshape(1)
+
+
+def gauss_ell(y, mu, v, noise, scale, _form=''):
+    """out[s] = scale * sum_i E_q log N(y_i | f_si, noise);  mu, v:(S,n)  y:(n,)  noise: 1-element tensor."""
+    ref, y, mu, v, noise = _gauss_args(y, mu, v, noise, f'gauss_ell{_form}')
     S, n = mu.shape
-    if y.shape != (n,) or v.shape != mu.shape:
-        raise BackendError('gauss_ell: shapes')
-    out = torch.empty(S, dtype=ref.dtype, device=ref.device)
+    out = torch.empty(1 if _form else S, dtype=ref.dtype, device=ref.device)
     ws = _red_ws(ref)
-    _lib.call(f'nsgp_gauss_ell_fwd_{_sfx(ref)}', _p(y), _p(mu), _p(v), _p(noise.reshape(1)), S, n, float(scale),
-              _p(out), _p(ws), ws.numel(), _stream())
+    _lib.call(f'nsgp_gauss_ell{_form}_fwd_{_sfx(ref)}', _p(y), _p(mu), _p(v), _p(noise), S, n, float(scale), _p(out), _p(ws),
+              ws.numel(), _stream())
     return out
 
 
-def gauss_ell_bwd(y, mu, v, noise, scale, gout, need_noise=True):
-    ref = _chk(y, mu, v, noise, gout)
-    y, mu, v, gout = _c(y), _c(mu), _c(v), _c(gout)
+def gauss_ell_bwd(y, mu, v, noise, scale, gout, need_noise=True, _form=''):
+    """(gmu, gv, gnoise or None) of gauss_ell for the upstream gradient gout:(S,), a device tensor."""
+    ref, y, mu, v, noise = _gauss_args(y, mu, v, noise, f'gauss_ell{_form}_bwd')
+    _chk(ref, gout)
     S, n = mu.shape
-    if gout.shape != (S,):
-        raise BackendError('gauss_ell_bwd: gout must be (S,)')
+    if gout.numel() != (1 if _form else S):
+        raise BackendError(f'gauss_ell{_form}_bwd: gout must have {"1 element" if _form else "S elements"}')
     gmu, gv = torch.empty_like(mu), torch.empty_like(mu)
     gn = torch.empty(1, dtype=ref.dtype, device=ref.device) if need_noise else None
     ws = _red_ws(ref)
-    _lib.call(f'nsgp_gauss_ell_bwd_{_sfx(ref)}', _p(y), _p(mu), _p(v), _p(noise.reshape(1)), S, n, float(scale),
-              _p(gout), _p(gmu), _p(gv), _p(gn), _p(ws), ws.numel(), _stream())
+    _lib.call(f'nsgp_gauss_ell{_form}_bwd_{_sfx(ref)}', _p(y), _p(mu), _p(v), _p(noise), S, n, float(scale),
+              _p(_c(gout).reshape(-1)), _p(gmu), _p(gv), _p(gn), _p(ws), ws.numel(), _stream())
     return gmu, gv, gn
 
 
-def kl_whitened(m, Lq):
+def gauss_ell_total(y, mu, v, noise, scale):
+    """1-element tensor  scale * sum_s sum_i E_q log N(y_i | f_si, noise): gauss_ell and the sum over s as ONE reduction."""
+    return gauss_ell(y, mu, v, noise, scale, _form='_total')
+
+
+def gauss_ell_total_bwd(y, mu, v, noise, scale, gout, need_noise=True):
+    """(gmu, gv, gnoise or None) of gauss_ell_total for the upstream gradient gout (a 1-element device tensor)."""
+    return gauss_ell_bwd(y, mu, v, noise, scale, gout, need_noise, _form='_total')
+
+
+def _kl_whitened_args(m, Lq, what):
     ref = _chk(m, Lq)
-    m, Lq = _c(m), _c(Lq)
-    if m.dim() == 1:
-        m, Lq = m.unsqueeze(0), Lq.unsqueeze(0)
-    batch, M = m.shape
-    if Lq.shape != (batch, M, M):
-        raise BackendError('kl_whitened: shapes')
-    out = torch.empty(batch, dtype=ref.dtype, device=ref.device)
+    m2, L2 = _c(m), _c(Lq)
+    if m2.dim() == 1:
+        m2, L2 = m2.unsqueeze(0), L2.unsqueeze(0)
+    if m2.dim() != 2 or L2.shape != (*m2.shape, m2.shape[1]):
+        raise BackendError(f'{what}: m, Lq must be (b,M), (b,M,M) or (M,), (M,M)')
+    return ref, m2, L2
+
+
+def _grad_out(t):
+    """Where the FIRST kernel to write t's gradient writes it: the optimiser's gradient bucket when t is a registered
+    parameter whose range nothing has written yet (see grad_sink), else a fresh buffer."""
+    sink = grad_sink(t)
+    return sink[0] if (sink is not None and not sink[1]) else torch.empty_like(t)
+
+
+def kl_whitened(m, Lq):
+    """out[b] = KL(N(m_b, Lq_b Lq_b^T) || N(0, I));  m, Lq:(b,M), (b,M,M) or (M,), (M,M)."""
+    ref, m, Lq = _kl_whitened_args(m, Lq, 'kl_whitened')
+    out = torch.empty(m.shape[0], dtype=ref.dtype, device=ref.device)
     ws = _red_ws(ref)
-    _lib.call(f'nsgp_kl_whitened_fwd_{_sfx(ref)}', _p(m), _p(Lq), batch, M, _p(out), _p(ws), ws.numel(), _stream())
+    _lib.call(f'nsgp_kl_whitened_fwd_{_sfx(ref)}', _p(m), _p(Lq), *m.shape, _p(out), _p(ws), ws.numel(), _stream())
     return out
 
 
 def kl_whitened_bwd(m, Lq, gout):
-    ref = _chk(m, Lq)
-    shp_m, shp_L = m.shape, Lq.shape
-    m, Lq = _c(m), _c(Lq)
-    if m.dim() == 1:
-        m, Lq = m.unsqueeze(0), Lq.unsqueeze(0)
-    batch, M = m.shape
-    gm, gL = torch.empty_like(m), torch.empty_like(Lq)
-    _lib.call(f'nsgp_kl_whitened_bwd_{_sfx(ref)}', _p(m), _p(Lq), batch, M, float(gout), _p(gm), _p(gL), _stream())
-    return gm.reshape(shp_m), gL.reshape(shp_L)
+    ref, m2, L2 = _kl_whitened_args(m, Lq, 'kl_whitened_bwd')
+    gm, gL = torch.empty_like(m2), torch.empty_like(L2)
+    _lib.call(f'nsgp_kl_whitened_bwd_{_sfx(ref)}', _p(m2), _p(L2), *m2.shape, float(gout), _p(gm), _p(gL), _stream())
+    return gm.reshape(m.shape), gL.reshape(Lq.shape)
+
+
+def _addin_arg(ref, addin, what):
+    if addin is None:
+        return None
+    _chk(ref, addin)
+    if addin.numel() != 1:
+        raise BackendError(f'{what}: addin must be a scalar')
+    return _p(_c(addin).reshape(1))
+
+
+def kl_whitened_total(m, Lq, scale=1.0, addin=None):
+    """1-element tensor  addin + scale * sum_b KL(N(m_b, Lq_b Lq_b^T) || N(0, I))  (addin: optional scalar tensor, so the
+    terms of an objective chain without separate additions)."""
+    ref, m2, L2 = _kl_whitened_args(m, Lq, 'kl_whitened_total')
+    if m2.shape[0] == 0:
+        raise BackendError('kl_whitened_total: empty batch')
+    out = torch.empty(1, dtype=ref.dtype, device=ref.device)
+    ws = _red_ws(ref)
+    _lib.call(f'nsgp_kl_whitened_total_acc_fwd_{_sfx(ref)}', _p(m2), _p(L2), *m2.shape, float(scale),
+              _addin_arg(ref, addin, 'kl_whitened_total'), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def kl_whitened_total_bwd(m, Lq, scale, gout):
+    """(gm, gLq) of kl_whitened_total for the upstream gradient gout (a 1-element device tensor), in m's / Lq's shapes."""
+    ref, m2, L2 = _kl_whitened_args(m, Lq, 'kl_whitened_total_bwd')
+    _chk(ref, gout)
+    gm, gL = torch.empty_like(m2), _grad_out(L2)
+    _lib.call(f'nsgp_kl_whitened_total_bwd_{_sfx(ref)}', _p(m2), _p(L2), *m2.shape, float(scale), _p(_c(gout).reshape(1)),
+              _p(gm), _p(gL), _stream())
+    return gm.reshape(m.shape), gL.reshape(Lq.shape)
 
 
 def philox_normal(seed, stream_id, row0, S, n, b, dtype=torch.float32, device='cuda', step_dev=None):
@@ -1449,75 +1500,42 @@ class GaussEllTotalFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, mu, v, noise, scale):
-        ref = _chk(y, mu, v, noise)
-        y, mu, v = _c(y), _c(mu), _c(v)
-        S, n = mu.shape
-        if y.shape != (n,) or v.shape != mu.shape:
-            raise BackendError('gauss_ell_total: shapes')
-        out = torch.empty(1, dtype=ref.dtype, device=ref.device)
-        ws = _red_ws(ref)
-        _lib.call(f'nsgp_gauss_ell_total_fwd_{_sfx(ref)}', _p(y), _p(mu), _p(v), _p(noise.reshape(1)), S, n, float(scale),
-                  _p(out), _p(ws), ws.numel(), _stream())
         ctx.save_for_backward(y, mu, v, noise)
         ctx.scale = float(scale)
-        return out.reshape(())
+        return gauss_ell_total(y, mu, v, noise, scale).reshape(())
 
     @staticmethod
     def backward(ctx, g):
         y, mu, v, noise = ctx.saved_tensors
-        S, n = mu.shape
-        gmu, gv = torch.empty_like(mu), torch.empty_like(mu)
-        need_noise = ctx.needs_input_grad[3]
-        gn = torch.empty(1, dtype=mu.dtype, device=mu.device) if need_noise else None
-        ws = _red_ws(mu)
-        _lib.call(f'nsgp_gauss_ell_total_bwd_{_sfx(mu)}', _p(y), _p(mu), _p(v), _p(noise.reshape(1)), S, n, ctx.scale,
-                  _p(_c(g).reshape(1)), _p(gmu), _p(gv), _p(gn), _p(ws), ws.numel(), _stream())
+        gmu, gv, gn = gauss_ell_total_bwd(y, mu, v, noise, ctx.scale, g, need_noise=ctx.needs_input_grad[3])
         return None, gmu, gv, gn.reshape(noise.shape) if gn is not None else None, None
 
 
 class KlWhitenedTotalFn(torch.autograd.Function):
-    """Scalar  addin + scale * sum_b KL(N(m_b, Lq_b Lq_b^T) || N(0, I))  (addin: optional scalar tensor, so the terms of
-    an objective chain without separate additions); backward reads the upstream gradient on the device."""
+    """Scalar  addin + scale * sum_b KL(N(m_b, Lq_b Lq_b^T) || N(0, I))  (kl_whitened_total); backward reads the upstream
+    gradient on the device and is the first writer of Lq's range of the gradient bucket (see grad_sink)."""
 
     @staticmethod
     def forward(ctx, m, Lq, scale, addin=None):
-        ref = _chk(m, Lq)
-        m2, L2 = _c(m), _c(Lq)
-        if m2.dim() == 1:
-            m2, L2 = m2.unsqueeze(0), L2.unsqueeze(0)
-        batch, M = m2.shape
-        if L2.shape != (batch, M, M) or batch == 0:
-            raise BackendError('kl_whitened_total: shapes')
-        if addin is not None:
-            _chk(ref, addin)
-            if addin.numel() != 1:
-                raise BackendError('kl_whitened_total: addin must be a scalar')
-        out = torch.empty(1, dtype=ref.dtype, device=ref.device)
-        ws = _red_ws(ref)
-        _lib.call(f'nsgp_kl_whitened_total_acc_fwd_{_sfx(ref)}', _p(m2), _p(L2), batch, M, float(scale),
-                  None if addin is None else _p(_c(addin).reshape(1)), _p(out), _p(ws), ws.numel(), _stream())
-        ctx.save_for_backward(m2, L2)
-        ctx.scale, ctx.shapes, ctx.has_addin = float(scale), (m.shape, Lq.shape), addin is not None
+        out = kl_whitened_total(m, Lq, scale, addin)
+        ctx.save_for_backward(m, Lq)
+        ctx.scale, ctx.has_addin = float(scale), addin is not None
         return out.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        m2, L2 = ctx.saved_tensors
-        batch, M = m2.shape
-        sink = grad_sink(L2)                 # first writer of the gradient bucket's range for Lq (see grad_sink)
-        gm = torch.empty_like(m2)
-        gL = sink[0] if (sink is not None and not sink[1]) else torch.empty_like(L2)
-        _lib.call(f'nsgp_kl_whitened_total_bwd_{_sfx(m2)}', _p(m2), _p(L2), batch, M, ctx.scale, _p(_c(g).reshape(1)),
-                  _p(gm), _p(gL), _stream())
-        return gm.reshape(ctx.shapes[0]), gL.reshape(ctx.shapes[1]), None, (g if ctx.has_addin else None)
+        m, Lq = ctx.saved_tensors
+        gm, gL = kl_whitened_total_bwd(m, Lq, ctx.scale, g)
+        return gm, gL, None, (g if ctx.has_addin else None)
 
 
 class KlMeanFieldTotalFn(torch.autograd.Function):
     """Scalar  addin + scale * sum_b KL(N(m_b, diag(s2_b)) || N(0, I))  -- KlWhitenedTotalFn for a mean-field q(u);
-    m, s2:(b,M) or (M,), s2 the variances.  backward reads the upstream gradient on the device."""
+    m, s2:(b,M) or (M,), s2 the variances.  backward reads the upstream gradient on the device.  With scale 1 and no addin
+    it is the whitened VariationalStrategy.kl_divergence of a mean-field q(u)."""
 
     @staticmethod
-    def forward(ctx, m, s2, scale, addin=None):
+    def forward(ctx, m, s2, scale=1.0, addin=None):
         out = kl_meanfield_total(m, s2, scale, addin)
         ctx.save_for_backward(m, s2)
         ctx.scale, ctx.has_addin = float(scale), addin is not None
@@ -1530,18 +1548,7 @@ class KlMeanFieldTotalFn(torch.autograd.Function):
         return gm, gs2, None, (g if ctx.has_addin else None)
 
 
-class KlMeanFieldFn(torch.autograd.Function):
-    """sum_b KL(N(m_b, diag(s2_b)) || N(0, I))   (whitened VariationalStrategy.kl_divergence of a mean-field q(u))."""
-
-    @staticmethod
-    def forward(ctx, m, s2):
-        ctx.save_for_backward(m, s2)
-        return kl_meanfield_total(m, s2).reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        m, s2 = ctx.saved_tensors
-        return kl_meanfield_total_bwd(m, s2, 1.0, g)
+KlMeanFieldFn = KlMeanFieldTotalFn                       # apply(m, s2): the name tests/test_gpu_meanfield.py knows
 
 
 class DsviObjectiveFn(torch.autograd.Function):
@@ -1566,15 +1573,10 @@ class DsviObjectiveFn(torch.autograd.Function):
         S, n = mu.shape
         if y.shape != (n,) or v.shape != mu.shape or len(mL) % 2 or len(mL) > 16:
             raise BackendError('dsvi_objective: shapes')
-        ms, Ls = [], []
-        for m, Lq in zip(mL[0::2], mL[1::2]):
-            m2, L2 = _c(m), _c(Lq)
-            if m2.dim() == 1:
-                m2, L2 = m2.unsqueeze(0), L2.unsqueeze(0)
-            ms.append(m2)
-            Ls.append(L2)
+        groups = [_kl_whitened_args(m, Lq, 'dsvi_objective')[1:] for m, Lq in zip(mL[0::2], mL[1::2])]
+        ms, Ls = [m2 for m2, _ in groups], [L2 for _, L2 in groups]
         M = ms[0].shape[1] if ms else 0
-        if any(m2.shape[1] != M or L2.shape != (m2.shape[0], M, M) for m2, L2 in zip(ms, Ls)):
+        if any(m2.shape[1] != M for m2 in ms):
             raise BackendError('dsvi_objective: every group must be (b,M) / (b,M,M) with one M')
         out = torch.empty(1, dtype=ref.dtype, device=ref.device)
         lib = _lib.load()
@@ -1596,11 +1598,7 @@ class DsviObjectiveFn(torch.autograd.Function):
         gmu, gv = torch.empty_like(mu), torch.empty_like(mu)
         need_noise = ctx.needs_input_grad[3]
         gn = torch.empty(1, dtype=mu.dtype, device=mu.device) if need_noise else None
-        gms = [torch.empty_like(m2) for m2 in ms]
-        gLs = []
-        for L2 in Ls:                          # first writer of the gradient bucket's range for Lq (see grad_sink)
-            sink = grad_sink(L2)
-            gLs.append(sink[0] if (sink is not None and not sink[1]) else torch.empty_like(L2))
+        gms, gLs = [torch.empty_like(m2) for m2 in ms], [_grad_out(L2) for L2 in Ls]
         lib = _lib.load()
         ws = _ws(lib.nsgp_dsvi_objective_workspace(S, n, 0, 0, mu.element_size()), mu.device)
         _, pm, pL, nb = DsviObjectiveFn._arrays(ms, Ls)

@@ -46,7 +46,7 @@ def test_header_declares_and_library_exports_the_matern_entry_points():
     raw = ctypes.CDLL(nsgp.LIB_PATH)
     for name in want:
         assert hasattr(raw, name), name
-    assert lib.nsgp_abi_version() == 1
+    assert lib.nsgp_abi_version() == 2
     # host-only size query: the RBF workspace layout (same accumulator counts)
     assert lib.nsgp_matern_build_bwd_workspace(2, 300, 500, 3, 8) == lib.nsgp_rbf_build_bwd_workspace(2, 300, 500, 3, 8)
 

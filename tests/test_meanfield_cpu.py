@@ -169,7 +169,7 @@ def _P(o):
 def test_new_entry_points_are_exported_and_validate_their_arguments_on_the_host():
     import nsgp
     lib = nsgp.load_library()
-    assert lib.nsgp_abi_version() == 1
+    assert lib.nsgp_abi_version() == 2
     names = nsgp.declared_symbols()
     for stem in ('svgp_diag_colsq', 'svgp_colstats_finalize_diag', 'svgp_diag_bwd', 'kl_meanfield_total_acc_fwd',
                  'kl_meanfield_total_bwd'):

@@ -53,6 +53,12 @@ def kl_blocks(M):
     return min(max(cdiv(M * M, 1024), 1), 256)
 
 
+def kl_diag_blocks(tot):
+    """csrc/svgp.hip kl_diag_blocks: blocks of the mean-field KL's partial sums over all batch * M elements; each strides by
+    nblk * 256."""
+    return min(cdiv(tot, 1024), 256)
+
+
 def rowdot_chunks(n, dt):
     """rowdot_affine_kernel: chunks of 256 lanes x 16 bytes per row."""
     return cdiv(n, 256 * (4 if dt == 'f32' else 2))
@@ -221,6 +227,29 @@ def kl_inputs(case, mode):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# mean-field KL (bit record only: tests/test_gpu_meanfield.py holds its values to the oracle)
+# ---------------------------------------------------------------------------------------------------------------------------
+MfKlCase = collections.namedtuple('MfKlCase', 'batch M')
+# MF_KL_CASES_BEGIN
+MF_KL_CASES = [MfKlCase(b, M) for b, M in ((1, 1), (1, 255), (1, 257), (1, 1024), (1, 1025), (3, 342), (2, 131073))]
+# MF_KL_CASES_END
+# value and gradients as tests/test_gpu_meanfield.py::test_mean_field_kl_matches_oracle_and_accumulates judges them
+MF_KL_TOL = {'f32': dict(rtol=2e-5, atol=1e-6), 'f64': dict(rtol=1e-12, atol=1e-13)}
+
+
+def mf_kl_inputs(case):
+    """m normal, variances s2 uniform in [0.25, 2.25]; scale, addin and upstream gradient of the whitened KL's total form."""
+    g = gen(f'mfkl-{case.batch}-{case.M}')
+    return dict(m=normal32(case, g), s2=uniform32(case, g, 0.25, 2.25), scale=KL_SCALE, addin=0.40625, up=KL_UP)
+
+
+def mf_kl_reference(P):
+    """(sum_b KL(N(m_b, diag(s2_b)) || N(0, I)), gm, gs2 for a unit upstream factor), float64."""
+    m, s2 = P['m'], P['s2']
+    return float(0.5 * ((s2 - 1.0) - s2.log() + m * m).sum()), m, 0.5 * (1.0 - 1.0 / s2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # fused DSVI objective
 # ---------------------------------------------------------------------------------------------------------------------------
 # squeeze: groups of batch 1 are handed over as (M,) / (M, M).  up: the upstream gradient of the scalar.
@@ -276,6 +305,19 @@ def obj_reference(P):
         k, ka = kl_reference(m, L)
         val, ab = val + P['kl_scale'] * k.sum(), ab + abs(P['kl_scale']) * ka.sum()
     return float(val), float(ab), P['ell_scale'] * t
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the objective's bit record (tools/record_objective_hashes.py, tests/test_gpu_objective_bits.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+# (kind, row of the kind's table, dtype): every row above that feeds an entry point of the DSVI objective, in both dtypes
+OBJECTIVE_BITS_CASES = [(kind, c, dt) for kind, table in (('gauss', GAUSS_CASES), ('kl', KL_CASES), ('obj', OBJ_CASES),
+                                                          ('mfkl', MF_KL_CASES)) for c in table for dt in DTYPES]
+
+
+def objective_bits_id(run):
+    kind, c, dt = run
+    return '-'.join([kind] + ([c.name] if kind == 'obj' else [str(f) for f in c]) + [dt])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -497,6 +539,29 @@ def test_objective_table_hits_every_boundary():
     assert any(c.squeeze and 1 in c.batches for c in OBJ_CASES)
     assert any((not c.squeeze and 1 in c.batches) or max(c.batches, default=0) > 1 for c in OBJ_CASES)
     assert len({c.name for c in OBJ_CASES}) == len(OBJ_CASES)
+
+
+def test_mean_field_kl_table_hits_every_boundary():
+    tots = {c.batch * c.M for c in MF_KL_CASES}
+    assert {(c.batch, c.M) for c in MF_KL_CASES} >= {(1, 1), (1, 255), (1, 257), (1, 1024), (1, 1025), (3, 342), (2, 131073)}
+    assert 1 in tots and {255, 257} <= tots                            # one lane, both sides of a block's 256 lanes
+    assert {1024, 1025} <= tots and kl_diag_blocks(1024) == 1 and kl_diag_blocks(1025) == 2      # a block's share
+    assert any(c.batch > 1 and c.batch * c.M > 1024 and (c.batch * c.M) % 256 for c in MF_KL_CASES)   # batched, ragged
+    assert any(cdiv(t, 1024) > 256 and t % 1024 for t in tots)         # past the cap of 256 blocks: a ragged second trip
+    for c in MF_KL_CASES:
+        P = mf_kl_inputs(c)
+        assert P['m'].shape == tuple(c) and float(P['s2'].min()) >= 0.25 and float(P['s2'].max()) <= 2.25
+
+
+def test_objective_bit_record_holds_exactly_the_tables_rows():
+    import json
+    import os
+    ids = [objective_bits_id(r) for r in OBJECTIVE_BITS_CASES]
+    assert len(set(ids)) == len(ids) == 2 * (len(GAUSS_CASES) + len(KL_CASES) + len(OBJ_CASES) + len(MF_KL_CASES))
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'objective_hashes.json')) as f:
+        record = json.load(f)['cases']
+    assert sorted(record) == sorted(ids)
+    assert all(record[k] and all(len(h) == 64 for h in record[k].values()) for k in ids)
 
 
 def test_rowdot_table_hits_every_loop_boundary():
