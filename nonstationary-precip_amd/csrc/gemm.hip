@@ -23,14 +23,12 @@
 #include <type_traits>
 #include "common.h"
 
-#ifndef NSGP_F64ACC_BN
-#define NSGP_F64ACC_BN 64
-#endif
-#ifndef NSGP_F64ACC_BK
-#define NSGP_F64ACC_BK 16
-#endif
-
 namespace {
+
+constexpr int F64_BK = 16;           // K-tile depth of the plain float64 products (32: Cholesky adjoint faster, potrf N = 16384 slower)
+constexpr int F64_DEPTH = 2;         // register sets of loads in flight in the float64 DEEP loop (4, 6: potrf N = 4096 slower)
+constexpr int F64ACC_BN = 64;        // tile columns and K-tile depth of the float64-accumulating projections
+constexpr int F64ACC_BK = 16;
 
 #ifdef NSGP_GEMM_STAMPS
 // Diagnostic build only (tools/probes/gemm_stamps.py): one 16-word record per workgroup -- shader-clock stamps at entry,
@@ -213,40 +211,38 @@ struct TileLoader {
 // accumulation are float64.  This is the whitened projection A = L^-1 Kzx of the SVGP layer: the reference solves it
 // in float64 and rounds once; float32 accumulation of W Kzx loses 2e-4 at kappa(Kzz) ~ 1e6 (terms of size |W||K| ~ 80
 // cancel to O(1); tools/probes/whiten_precision.py), float64 accumulation reproduces the float64 solve to 3e-8.
-#ifndef NSGP_MIX_WG3
-#define NSGP_MIX_WG3 0
-#endif
-#ifndef NSGP_MIX_DEEP
-#define NSGP_MIX_DEEP 1
-#endif
-#ifndef NSGP_F32_DEEP
-#define NSGP_F32_DEEP 0
-#endif
-#ifndef NSGP_F64_BK
-#define NSGP_F64_BK 16
-#endif
-#ifndef NSGP_F64_DEPTH
-#define NSGP_F64_DEPTH 2
-#endif
-#ifndef NSGP_GEMM_ROLL
-#define NSGP_GEMM_ROLL 1
-#endif
-template <typename T, int BM, int BN, int BK, int MODE_A, int MODE_B, int EPI = 0, int KSC = 0, int PF = 0, int EDGE = 1,
-          int MIX = 0>
-__global__ __launch_bounds__(256, (BM == 128 && BN == 64 && (sizeof(T) == 4 || NSGP_MIX_WG3)) ? 3 : ((sizeof(T) == 8 && BM == 128 && BK == 32) ? 1 : 2)) void gemm_kernel(GemmArgs g, T alpha, const T* __restrict__ A,
+// LDS image of one <T, BM, BN, BK, MODE_A, MODE_B> tile: two buffers of the k-major images As[k][m], Bs[k][n] with padded
+// rows.  The kernel lays its shared memory out by this and the launcher sizes the dynamic region from it.
+template <typename T, int BM, int BN, int BK, int MODE_A, int MODE_B>
+struct TileLds {
+    static constexpr int PADA = (MODE_A == 0 && sizeof(T) == 4) ? 1 : Mfma<T>::PAD;
+    static constexpr int PADB = (MODE_B == 0 && sizeof(T) == 4) ? 1 : Mfma<T>::PAD;
+    static constexpr int LDA = BM + PADA, LDB = BN + PADB;
+    static constexpr size_t BYTES = 2 * BK * (LDA + LDB) * sizeof(T);
+};
+
+// Workgroups of a gemm_impl tile resident on one CU at a time (the planner's "slots" are 256 CUs x this): the 128 x 128
+// float32 tile holds 66 KB of LDS, the 128 x 64 one exists to fit three, the 64 x 64 tiles are bounded by their registers.
+constexpr int resident_wg_per_cu(size_t elem_size, bool big, bool narrow) { return big ? (narrow ? 3 : 2) : (elem_size == 4 ? 6 : 3); }
+// What __launch_bounds__ promises per CU.  3 for the float32 128 x 64 tile: the cap of 168 registers lets its third workgroup
+// fit.  2 otherwise: the 128-row tiles need up to 256 registers (three of the float64-accumulating one were tried: no faster).
+constexpr int launch_min_wg(size_t elem_size, int bm, int bn) { return (elem_size == 4 && bm == 128 && bn == 64) ? 3 : 2; }
+
+// EPI / KSC: fused epilogue and k-scaled loader, see `struct Epi`.
+template <typename T, int BM, int BN, int BK, int MODE_A, int MODE_B, int EPI = 0, int KSC = 0, int EDGE = 1, int MIX = 0>
+__global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_kernel(GemmArgs g, T alpha, const T* __restrict__ A,
                                                    const T* __restrict__ B, T beta, T* __restrict__ C,
                                                    T* __restrict__ slabs, Epi ep) {
-    static_assert(MIX == 0 || (sizeof(T) == 8 && EPI == 1 && KSC == 0 && PF == 0), "MIX: float64 colstats projection only");
+    static_assert(MIX == 0 || (sizeof(T) == 8 && EPI == 1 && KSC == 0), "MIX: float64 colstats projection only");
     static_assert(MIX != 2 || (EDGE == 0 && MODE_B == 1), "MIX = 2 (generated Kzx operand): whole tiles, n-contiguous pieces");
     using TB = std::conditional_t<MIX == 1 || MIX == 2, float, T>;   // element type of B in memory (MIX = 3: float64 B, float32 C)
     using TC = std::conditional_t<MIX != 0, float, T>;          // element type of C / rv / partials in memory
     using MF = Mfma<T>;
+    using LDS = TileLds<T, BM, BN, BK, MODE_A, MODE_B>;
     constexpr int MT = MF::MT, KS = MF::KS, NKK = BK / KS;
     constexpr int WM = BM / 2, WN = BN / 2;
     constexpr int TM = WM / MT, TN = WN / MT;
-    constexpr int PADA = (MODE_A == 0 && sizeof(T) == 4) ? 1 : MF::PAD;
-    constexpr int PADB = (MODE_B == 0 && sizeof(T) == 4) ? 1 : MF::PAD;
-    constexpr int LDA = BM + PADA, LDB = BN + PADB;
+    constexpr int LDA = LDS::LDA, LDB = LDS::LDB;
     constexpr int PA = BM * BK / 1024, PB = BN * BK / 1024;     // 4-element pieces per thread
     // all LDS in ONE dynamic region (the 128x128x32 f32 tile needs 66 KB > the 64 KB static limit)
     extern __shared__ __attribute__((aligned(32))) unsigned char gemm_smem[];
@@ -412,12 +408,11 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 64 && (sizeof(T) == 4 || N
     const T* ksb = KSC ? reinterpret_cast<const T*>(ep.ks) + bb * g.K : nullptr;
     const bool ks_vec = KSC && ((uintptr_t)ksb % (4 * sizeof(T)) == 0);
 
-    // per staging register set (the float64 loop keeps two tiles in flight): is the held tile a diagonal block of A / B, and its
-    // k0 - row0 offsets
-    // DEEP > 0 (plain float64 products on whole tiles): the K loop keeps DEEP register sets of loads in flight, see below
-    constexpr int DEEP = (sizeof(T) == 8 && KSC == 0 && EDGE == 0 && PF == 0 && ((MIX == 0 && EPI == 0) || (MIX != 0 && NSGP_MIX_DEEP))) ? NSGP_F64_DEPTH
-                         : ((sizeof(T) == 4 && KSC == 0 && EDGE == 0 && NSGP_F32_DEEP > 0) ? NSGP_F32_DEEP : 0);
+    // DEEP > 0: float64 on whole tiles, plain or float64-accumulating (MIX) -- one K loop with DEEP register sets of loads in flight
+    constexpr int DEEP = (sizeof(T) == 8 && KSC == 0 && EDGE == 0 && (MIX != 0 || EPI == 0)) ? F64_DEPTH : 0;
     constexpr int NSET = DEEP > 2 ? DEEP : 2;
+    // per staging register set (the float64 loops keep two tiles in flight): is the held tile a diagonal block of A / B, and its
+    // k0 - row0 offsets
     bool st_adiag[NSET] = {}, st_bdiag[NSET] = {};
     int st_ad[NSET] = {}, st_bd[NSET] = {};
     auto load_ks = [&](int64_t k0) __attribute__((always_inline)) {
@@ -659,7 +654,7 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 64 && (sizeof(T) == 4 || N
             // no branch at all -- bare vector loads, every MFMA, every staging store.  With the choice between loader paths /
             // MFMA masks inside ONE loop hipcc carried the accumulators and the staging registers through phi copies (two
             // register sets, 64 v_mov per K-tile, spills inside the loop).
-            // ROLL (float32 kernels, NSGP_GEMM_ROLL): the hot loop also takes the diagonal blocks of triangular operands -- they
+            // ROLL (float32 kernels): the hot loop also takes the diagonal blocks of triangular operands -- they
             // are masked as they are stored, and a wave whose rows / columns lie entirely in an operand's zero part for a
             // stretch of K-tiles runs a copy of the loop without the MFMAs for that stretch (below) -- so "regular" only means
             // "whole".  (A deeper prefetch was tried on top: the load of the K-tile after next issued INTO the registers whose
@@ -668,7 +663,8 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 64 && (sizeof(T) == 4 || N
             // on its SIMD went from 5400 to 5280 cycles per 4096-cycle K-tile: the stall is not in the loads; and hipcc may
             // copy an asm-loaded register before the hand-placed wait -- it did in the 64 x 64 kernel's last tile, wrong
             // results.  Dropped.)
-            constexpr bool ROLL = NSGP_GEMM_ROLL && sizeof(T) == 4 && KSC == 0;
+            // ROLL: every float32 product without the k-scaled loader
+            constexpr bool ROLL = sizeof(T) == 4 && KSC == 0;
             auto regular = [&](int t) __attribute__((always_inline)) {
                 const int64_t k0 = kbeg + (int64_t)t * BK;
                 if (k0 + BK > kend) return false;
@@ -717,6 +713,7 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 64 && (sizeof(T) == 4 || N
             // issued at the top of a tile has not landed when its first store comes up (wait_any 20 % of wave time).
             // DEPTH2 keeps TWO K-tiles of loads in flight in two register sets: tile t stores the set loaded during tile
             // t - 1 and issues the loads of tile t + 2.
+            // DEPTH2: the float64 products that DEEP leaves (ragged, or fused on whole tiles), without the k-scaled loader
             constexpr bool DEPTH2 = sizeof(T) == 8 && KSC == 0;
             int hend = h0;                                                   // first tile the hot loop did NOT run
             if constexpr (ROLL) {
@@ -806,7 +803,7 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 64 && (sizeof(T) == 4 || N
                     hend = h1;
                 }
             }
-            if (!ROLL && !DEPTH2 && h1 > h0) {
+            if (!ROLL && !DEPTH2 && h1 > h0) {                  // the k-scaled loader (Lqbar): the bare hot loop
                 const T* pa = la.cur + (int64_t)(h0 + 1) * BK * la.kstep;
                 const TB* pb = lb.cur + (int64_t)(h0 + 1) * BK * lb.kstep;
                 const int64_t da = (int64_t)BK * la.kstep, db = (int64_t)BK * lb.kstep;
@@ -1034,6 +1031,27 @@ __global__ void splitk_reduce_kernel(GemmArgs g, T alpha, const T* __restrict__ 
 
 struct Plan { int big, narrow; int64_t ksplit, kper; };
 
+// The A/B switches of tools/gemm_bench.py, read once per call of an entry point (the tool toggles them inside one process).
+struct GemmEnv {
+    bool no_xcd;            // NSGP_GEMM_NO_XCD=1: no XCD-aware tile order
+    int xcd_group;          // NSGP_GEMM_XCD_GROUP: 1 = half the tile rows per group, r > 1 = r rows per group (default off)
+    char batch_perm;        // NSGP_GEMM_BATCH_PERM: '0' = off, '1' = single-round launches only, unset (0) = default
+    bool force_narrow;      // NSGP_GEMM_FORCE_NARROW=1: 128 x 64 tiles for every single-pass triangular-A launch
+    size_t lds_extra;       // NSGP_GEMM_LDS_EXTRA (bytes): occupancy experiment -- extra dynamic LDS, e.g. 40000 leaves one workgroup per CU
+};
+static inline GemmEnv gemm_env() {
+    const char* no_xcd = getenv("NSGP_GEMM_NO_XCD");
+    const char* grp = getenv("NSGP_GEMM_XCD_GROUP");
+    const char* bpe = getenv("NSGP_GEMM_BATCH_PERM");
+    const char* fn = getenv("NSGP_GEMM_FORCE_NARROW");
+    const char* xe = getenv("NSGP_GEMM_LDS_EXTRA");
+    return GemmEnv{no_xcd && no_xcd[0] == '1', grp ? atoi(grp) : 0, bpe ? bpe[0] : (char)0, fn && fn[0] == '1',
+                   xe ? (size_t)atoi(xe) : 0};
+}
+
+// K-tile depth of a gemm_impl tile (plain: no fused epilogue / operand scaling)
+template <typename T> constexpr int tile_bk(int bm, bool plain) { return bm == 128 ? 32 : ((sizeof(T) == 8 && plain) ? F64_BK : 16); }
+
 static inline int64_t active_tiles(int64_t M, int64_t N, int64_t bm, int flags) {
     const int64_t tm = cdiv64(M, bm), tn = cdiv64(N, bm);
     if (!(flags & NSGP_GEMM_C_LOWER)) return tm * tn;
@@ -1042,11 +1060,12 @@ static inline int64_t active_tiles(int64_t M, int64_t N, int64_t bm, int flags) 
     return cnt;
 }
 
-// Tile size and K-split.  Resident workgroups ("slots") = 256 CUs x blocks/CU for the kernel variant
-// (2 for the 128x128 f32 tile, 6 / 3 for the 64x64 f32 / f64 tiles); the number of rounds the grid needs
+// Tile size and K-split.  Resident workgroups ("slots") = 256 CUs x resident_wg_per_cu of the tile (the narrow tile is
+// chosen afterwards and does not enter the cost); the number of rounds the grid needs
 // is ceil(active_blocks / slots), so the K-split is chosen to minimise rounds x K-tiles per block plus
 // the slab traffic of the split (measured: 792 active blocks on 512 slots ran 905 us, CUs 55 % busy).
-template <typename T> Plan make_plan(int64_t M, int64_t N, int64_t K, int64_t nb, int flags, bool allow_big = true) {
+template <typename T> Plan make_plan(int64_t M, int64_t N, int64_t K, int64_t nb, int flags, bool allow_big = true,
+                                      const GemmEnv& env = gemm_env()) {
     Plan p;
     const bool can_split = !(flags & NSGP_GEMM_NO_SPLITK) && K >= 512;
     int64_t maxks = can_split ? K / 256 : 1;
@@ -1058,7 +1077,7 @@ template <typename T> Plan make_plan(int64_t M, int64_t N, int64_t K, int64_t nb
     p.big = allow_big && sizeof(T) == 4 && tiles_big * maxks >= 256;
     const int64_t bm = p.big ? 128 : 64;
     const int64_t tiles = active_tiles(M, N, bm, flags) * nb;
-    const int64_t slots = 256 * (p.big ? 2 : (sizeof(T) == 4 ? 6 : 3));
+    const int64_t slots = 256 * resident_wg_per_cu(sizeof(T), p.big, false);
     const int64_t ktiles = cdiv64(K, 16);
     int64_t best_ks = 1;
     double best_cost = 1e300;
@@ -1083,11 +1102,8 @@ template <typename T> Plan make_plan(int64_t M, int64_t N, int64_t K, int64_t nb
     // the tile count at half the work each, so short tiles back-fill behind the long ones.
     p.narrow = p.big && p.ksplit == 1 && !(flags & NSGP_GEMM_C_LOWER) &&
                (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER)) && tiles_big <= slots;
-    {   // experiment switch: 128 x 64 tiles (three workgroups per CU) for every single-pass triangular-A launch
-        const char* fn = getenv("NSGP_GEMM_FORCE_NARROW");
-        if (fn && fn[0] == '1' && p.big && p.ksplit == 1 && !(flags & NSGP_GEMM_C_LOWER) &&
-            (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER))) p.narrow = 1;
-    }
+    if (env.force_narrow && p.big && p.ksplit == 1 && !(flags & NSGP_GEMM_C_LOWER) &&
+        (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER))) p.narrow = 1;
     return p;
 }
 
@@ -1103,12 +1119,13 @@ struct Order {
 };
 
 template <typename T>
-Order plan_order(const Plan& p, int64_t M, int64_t N, int64_t K, int64_t nb, int flags, bool plain, int vecA, int vecB) {
+Order plan_order(const Plan& p, int64_t M, int64_t N, int64_t K, int64_t nb, int flags, bool plain, int vecA, int vecB,
+                 const GemmEnv& env) {
     Order o;
     const int64_t bmn = p.big ? 128 : 64;
     o.bm = (int)bmn;
     o.bn = p.narrow ? 64 : (int)bmn;
-    o.bk = bmn == 128 ? 32 : ((sizeof(T) == 8 && plain) ? NSGP_F64_BK : 16);
+    o.bk = tile_bk<T>(o.bm, plain);
     o.tiles_m = cdiv64(M, bmn);
     o.tiles_n = cdiv64(N, o.bn);
     const int64_t ngrid = (flags & NSGP_GEMM_C_LOWER) ? active_tiles(M, N, bmn, flags) : o.tiles_m * o.tiles_n;
@@ -1116,13 +1133,12 @@ Order plan_order(const Plan& p, int64_t M, int64_t N, int64_t K, int64_t nb, int
     o.xcd_group = 0;
     o.xcd_chunk = 0;
     o.batch_perm = 0;
-    const char* no_xcd = getenv("NSGP_GEMM_NO_XCD");              // A/B switches for tools/gemm_bench.py
-    const bool xcd_ok = !(no_xcd && no_xcd[0] == '1');
+    const bool xcd_ok = !env.no_xcd;
+    const int64_t slots = 256 * resident_wg_per_cu(sizeof(T), p.big, p.narrow);
     // The column-panel-grouped order is OFF by default: it cuts the fabric traffic of the projections ~3x, but the
     // hardware deals workgroups to the XCDs in strict rotation, so tiles of unequal length in flight stall the
     // dispatcher (measured: 611 us grouped vs 472 us in the row-major longest-first order, M=1024, n=40960).
-    const char* grp = getenv("NSGP_GEMM_XCD_GROUP");
-    const int grp_rows = grp ? atoi(grp) : 0;                       // 1: half the tile rows per group; r > 1: r rows per group
+    const int grp_rows = env.xcd_group;
     const bool group_ok = grp_rows >= 1;
     if (xcd_ok && group_ok && !(flags & NSGP_GEMM_C_LOWER) && p.ksplit == 1 && o.tiles_n >= 16 && o.tiles_m <= 64 &&
         !(flags & (NSGP_GEMM_B_LOWER | NSGP_GEMM_B_UPPER))) {
@@ -1140,15 +1156,11 @@ Order plan_order(const Plan& p, int64_t M, int64_t N, int64_t K, int64_t nb, int
     } else if (p.ksplit == 1 && nb > 1 && (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER | NSGP_GEMM_B_LOWER |
                                                      NSGP_GEMM_B_UPPER | NSGP_GEMM_C_LOWER))) {
         // batched triangular launch that fits one round of resident workgroups: complementary tile orders per batch element
-        const int64_t slots = 256 * (p.big ? (p.narrow ? 3 : 2) : (sizeof(T) == 4 ? 6 : 3));
-        const char* bpe = getenv("NSGP_GEMM_BATCH_PERM");            // A/B switch (default on)
         // (more rounds: batch element fastest -- hidden layer, n = 4096 x 2 GPs: 234 -> 225 us for the forward pair)
-        if (!(bpe && bpe[0] == '0')) o.batch_perm = (ngrid * ngrid_y <= slots) ? 1 : ((bpe && bpe[0] == '1') ? 0 : 2);
+        if (env.batch_perm != '0') o.batch_perm = (ngrid * ngrid_y <= slots) ? 1 : (env.batch_perm == '1' ? 0 : 2);
     } else if (p.ksplit == 1 && nb == 1 && (flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER | NSGP_GEMM_B_LOWER |
                                                       NSGP_GEMM_B_UPPER | NSGP_GEMM_C_LOWER))) {
-        const int64_t slots = 256 * (p.big ? (p.narrow ? 3 : 2) : (sizeof(T) == 4 ? 6 : 3));
-        const char* bpe = getenv("NSGP_GEMM_BATCH_PERM");
-        if (ngrid > 256 && ngrid <= slots && !(bpe && bpe[0] == '0')) o.batch_perm = 3;       // snake (see the kernel)
+        if (ngrid > 256 && ngrid <= slots && env.batch_perm != '0') o.batch_perm = 3;       // snake (see the kernel)
     }
     o.grid_x = ngrid_x;
     o.grid_y = ngrid_y;
@@ -1160,17 +1172,102 @@ Order plan_order(const Plan& p, int64_t M, int64_t N, int64_t K, int64_t nb, int
 // what nsgp_gemm_plan reports (include/nsgp.h): the plan and order of a plain product
 template <typename T>
 void gemm_plan_fill(int64_t M, int64_t N, int64_t K, int64_t nb, int flags, int vec_a, int vec_b, int32_t* out) {
-    const Plan p = make_plan<T>(M, N, K, nb, flags);
-    const Order o = plan_order<T>(p, M, N, K, nb, flags, true, vec_a, vec_b);
+    const GemmEnv env = gemm_env();
+    const Plan p = make_plan<T>(M, N, K, nb, flags, true, env);
+    const Order o = plan_order<T>(p, M, N, K, nb, flags, true, vec_a, vec_b, env);
     out[0] = o.bm; out[1] = o.bn; out[2] = (int32_t)p.ksplit; out[3] = (int32_t)p.kper; out[4] = o.whole;
     out[5] = o.xcd_chunk > 0; out[6] = o.batch_perm; out[7] = (int32_t)o.grid_x; out[8] = (int32_t)o.grid_y;
+}
+
+// ---- the one launch path -------------------------------------------------------------------------------------------------
+// What a launch chooses at run time -- launch_gemm turns each into its template argument -- and the kernel's arguments.
+template <typename T> struct Launch {
+    int bm, bn;             // tile: 128 x 128, 128 x 64, 64 x 64 (float32); 64 x 64, and 128 x 64 / 64 x 64 with mix (float64)
+    int epi, ksc;           // fused epilogue (Epi::kind), k-scaled B loader
+    int edge;               // 1: bounds code (ragged or unaligned launch)
+    int mix;                // float64 accumulation on float32 data, see the kernel
+    GemmArgs g; Epi ep; dim3 grid; T alpha; const T *A, *B; T beta; T *C, *slabs; hipStream_t st;   // the kernel's arguments
+    size_t lds_extra;       // GemmEnv::lds_extra
+};
+
+template <typename T, int BM, int BN, int BK, int MA, int MB, int EPI, int KSC, int MIX>
+void launch_variant(const Launch<T>& l) {
+    constexpr size_t lds = TileLds<T, BM, BN, BK, MA, MB>::BYTES;
+    auto go = [&](auto kern) {
+        const size_t ldsx = lds + l.lds_extra;
+        nsgp_opt_in_lds((const void*)kern, ldsx);
+        hipLaunchKernelGGL(kern, l.grid, dim3(256), ldsx, l.st, l.g, l.alpha, l.A, l.B, l.beta, l.C, l.slabs, l.ep);
+    };
+    if constexpr (MIX == 2) {                       // the generated operand exists for whole tiles only (the caller checks)
+        go(gemm_kernel<T, BM, BN, BK, MA, MB, EPI, KSC, 0, MIX>);
+    } else {
+        if (l.edge) go(gemm_kernel<T, BM, BN, BK, MA, MB, EPI, KSC, 1, MIX>);
+        else go(gemm_kernel<T, BM, BN, BK, MA, MB, EPI, KSC, 0, MIX>);
+    }
+}
+
+// The (epilogue, loader, operand layout) combinations that exist for a tile (-31: none; the fused ones are the SVGP layer's).
+template <typename T, int BM, int BN, int MIX>
+int launch_tile(const Launch<T>& l) {
+    const int ma = l.g.modeA, mb = l.g.modeB;
+    if constexpr (MIX != 0) {                        // float64-accumulating column statistics: B contiguous along n
+        constexpr int BK = F64ACC_BK;
+        if constexpr (MIX == 1) {
+            if (ma == 1) launch_variant<T, BM, BN, BK, 1, 1, 1, 0, MIX>(l);
+            else launch_variant<T, BM, BN, BK, 0, 1, 1, 0, MIX>(l);
+        } else {
+            launch_variant<T, BM, BN, BK, 0, 1, 1, 0, MIX>(l);
+        }
+    } else if (l.epi == 0 && !l.ksc) {
+        constexpr int BK = tile_bk<T>(BM, true);
+        if (ma == 0 && mb == 0) launch_variant<T, BM, BN, BK, 0, 0, 0, 0, 0>(l);
+        else if (ma == 0) launch_variant<T, BM, BN, BK, 0, 1, 0, 0, 0>(l);
+        else if (mb == 0) launch_variant<T, BM, BN, BK, 1, 0, 0, 0, 0>(l);
+        else launch_variant<T, BM, BN, BK, 1, 1, 0, 0, 0>(l);
+    } else {
+        constexpr int BK = tile_bk<T>(BM, false);
+        if (l.epi == 1 && !l.ksc && ma == 0 && mb == 1) launch_variant<T, BM, BN, BK, 0, 1, 1, 0, 0>(l);
+        else if (l.epi == 1 && !l.ksc && ma == 1 && mb == 1) launch_variant<T, BM, BN, BK, 1, 1, 1, 0, 0>(l);
+        else if (l.epi == 2 && !l.ksc && ma == 0 && mb == 1) launch_variant<T, BM, BN, BK, 0, 1, 2, 0, 0>(l);
+        else if (l.epi == 0 && l.ksc && ma == 0 && mb == 0) launch_variant<T, BM, BN, BK, 0, 0, 0, 1, 0>(l);
+        else return -31;
+    }
+    return 0;
+}
+
+template <typename T>
+int launch_gemm(const Launch<T>& l) {
+    if constexpr (sizeof(T) == 4) {
+        if (l.bm == 128) return l.bn == 64 ? launch_tile<T, 128, 64, 0>(l) : launch_tile<T, 128, 128, 0>(l);
+        return launch_tile<T, 64, 64, 0>(l);
+    } else {
+        if (l.mix == 0) return launch_tile<T, 64, 64, 0>(l);
+        if (l.bm == 128) {
+            return l.mix == 1 ? launch_tile<T, 128, F64ACC_BN, 1>(l)
+                 : l.mix == 2 ? launch_tile<T, 128, F64ACC_BN, 2>(l) : launch_tile<T, 128, F64ACC_BN, 3>(l);
+        }
+        return l.mix == 1 ? launch_tile<T, 64, F64ACC_BN, 1>(l)
+             : l.mix == 2 ? launch_tile<T, 64, F64ACC_BN, 2>(l) : launch_tile<T, 64, F64ACC_BN, 3>(l);
+    }
+}
+
+// operand and output geometry of a launch, by name (the plan's fields are the caller's)
+static inline GemmArgs gemm_geometry(int64_t M, int64_t N, int64_t K, int64_t sam, int64_t sak, int64_t sa1, int64_t sa2,
+                                     int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2, int64_t ldc, int64_t sc1,
+                                     int64_t sc2, int64_t nb2) {
+    GemmArgs g{};
+    g.M = M; g.N = N; g.K = K;
+    g.sam = sam; g.sak = sak; g.sa1 = sa1; g.sa2 = sa2;
+    g.sbk = sbk; g.sbn = sbn; g.sb1 = sb1; g.sb2 = sb2;
+    g.ldc = ldc; g.sc1 = sc1; g.sc2 = sc2; g.nb2 = nb2;
+    return g;
 }
 
 template <typename T>
 int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam, int64_t sak, int64_t sa1,
               int64_t sa2, const T* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2, T beta, T* C,
               int64_t ldc, int64_t sc1, int64_t sc2, int64_t nb1, int64_t nb2, int flags, void* ws, size_t wsb,
-              void* stream, const Epi* epi = nullptr, int64_t* tiles_m_out = nullptr) {
+              void* stream, const Epi* epi = nullptr) {
     if (M < 0) return -1; if (N < 0) return -2; if (K < 0) return -3;
     if (nb1 < 1 || nb2 < 1) return -20;
     if (M == 0 || N == 0) return 0;
@@ -1179,16 +1276,13 @@ int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam,
     if ((flags & NSGP_GEMM_B_LOWER) && (flags & NSGP_GEMM_B_UPPER)) return -22;
     const int64_t nb = nb1 * nb2;
     const bool has_epi = epi && (epi->kind != 0 || epi->ks);
-    Plan p = make_plan<T>(M, N, K, nb, flags, !(has_epi && sizeof(T) == 8));   // fused variants: f64 on 64-tiles only
-    GemmArgs g;
-    g.M = M; g.N = N; g.K = K;
-    g.sam = sam; g.sak = sak; g.sa1 = sa1; g.sa2 = sa2;
-    g.sbk = sbk; g.sbn = sbn; g.sb1 = sb1; g.sb2 = sb2;
-    g.ldc = ldc; g.sc1 = sc1; g.sc2 = sc2; g.nb2 = nb2;
+    const GemmEnv env = gemm_env();
+    Plan p = make_plan<T>(M, N, K, nb, flags, !(has_epi && sizeof(T) == 8), env);   // fused variants: f64 on 64-tiles only
+    GemmArgs g = gemm_geometry(M, N, K, sam, sak, sa1, sa2, sbk, sbn, sb1, sb2, ldc, sc1, sc2, nb2);
     g.ksplit = p.ksplit; g.kper = p.kper; g.slab = nb * M * N; g.flags = flags;
     g.modeA = (sak == 1) ? 0 : (sam == 1 ? 1 : 0);
     g.modeB = (sbk == 1) ? 0 : (sbn == 1 ? 1 : 0);
-    if (epi && (epi->kind != 0 || epi->ks)) { g.modeA = epi->modeA; g.modeB = epi->modeB; }
+    if (has_epi) { g.modeA = epi->modeA; g.modeB = epi->modeB; }
     const size_t al = 4 * sizeof(T);
     auto vec_ok = [&](const void* ptr, int64_t unit, int64_t other, int64_t s1, int64_t s2) {
         return unit == 1 && other % 4 == 0 && s1 % 4 == 0 && s2 % 4 == 0 && ((uintptr_t)ptr % al) == 0;
@@ -1202,7 +1296,7 @@ int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam,
         slabs = (T*)ws;
     }
     hipStream_t st = (hipStream_t)stream;
-    const Order o = plan_order<T>(p, M, N, K, nb, flags, !has_epi, g.vecA, g.vecB);
+    const Order o = plan_order<T>(p, M, N, K, nb, flags, !has_epi, g.vecA, g.vecB, env);
     g.tiles_m = o.tiles_m;
     g.tiles_n = o.tiles_n;
     if (g.tiles_m * g.tiles_n > 2147483647LL || nb * g.ksplit > 65535) return -24;
@@ -1216,74 +1310,18 @@ int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam,
                 if (e != hipSuccess) return (int)e;
             }
     }
-    const int64_t ngrid_x = o.grid_x, ngrid_y = o.grid_y;
     g.xcd_group = o.xcd_group;
     g.xcd_chunk = o.xcd_chunk;
     g.batch_perm = o.batch_perm;
     g.part_rows = epi ? epi->part_rows : 0;
     g.nbk = (int)(nb * g.ksplit);
-    dim3 grid((unsigned)ngrid_x, (unsigned)ngrid_y, 1);
     Epi ep{};
     if (epi) ep = *epi;
-    if (tiles_m_out) *tiles_m_out = g.tiles_m;
     const int ekind = ep.kind, eks = ep.ks != nullptr;
     if (ekind != 0 && (g.ksplit != 1 || beta != T(0) || (flags & (NSGP_GEMM_C_LOWER | NSGP_GEMM_C_HALFDIAG)))) return -30;
-    const bool whole = o.whole;                      // whole, vector-loadable tiles everywhere -> the variant without bounds code
-    // launch<BM, BN, MA, MB, EP, KS>()  (the PF template slot, round 1's separate two-tiles-in-flight loop, is always 0 now)
-    auto launch = [&](auto bm_c, auto bn_c, auto ma_c, auto mb_c, auto ep_c, auto ks_c) {
-        constexpr int BM_ = decltype(bm_c)::value, BN_ = decltype(bn_c)::value, MA = decltype(ma_c)::value,
-                      MB = decltype(mb_c)::value, EP = decltype(ep_c)::value, KSv = decltype(ks_c)::value;
-        constexpr int BKc = (BM_ == 128 ? 32 : ((sizeof(T) == 8 && EP == 0 && KSv == 0) ? NSGP_F64_BK : 16));
-        constexpr int pa = (MA == 0 && sizeof(T) == 4) ? 1 : Mfma<T>::PAD;
-        constexpr int pb = (MB == 0 && sizeof(T) == 4) ? 1 : Mfma<T>::PAD;
-        constexpr size_t lds = 2 * BKc * ((BM_ + pa) + (BN_ + pb)) * sizeof(T);
-        auto go = [&](auto kern) {
-            // NSGP_GEMM_LDS_EXTRA (bytes): occupancy experiment -- extra dynamic LDS, e.g. 40000 leaves one workgroup per CU
-            static const char* xe = getenv("NSGP_GEMM_LDS_EXTRA");
-            const size_t ldsx = lds + (xe ? (size_t)atoi(xe) : 0);
-            nsgp_opt_in_lds((const void*)kern, ldsx);
-            hipLaunchKernelGGL(kern, grid, dim3(256), ldsx, st, g, alpha, A, B, beta, C, slabs, ep);
-        };
-        if (whole) go(gemm_kernel<T, BM_, BN_, BKc, MA, MB, EP, KSv, 0, 0>);
-        else go(gemm_kernel<T, BM_, BN_, BKc, MA, MB, EP, KSv, 0, 1>);
-    };
-#define IC(v) std::integral_constant<int, v>{}
-    // fused variants exist for the operand layouts the SVGP layer uses
-    auto launch_epi = [&](auto bm_c, auto bn_c) -> int {
-        if (ekind == 1 && !eks && g.modeA == 0 && g.modeB == 1) launch(bm_c, bn_c, IC(0), IC(1), IC(1), IC(0));
-        else if (ekind == 1 && !eks && g.modeA == 1 && g.modeB == 1) launch(bm_c, bn_c, IC(1), IC(1), IC(1), IC(0));
-        else if (ekind == 2 && !eks && g.modeA == 0 && g.modeB == 1) launch(bm_c, bn_c, IC(0), IC(1), IC(2), IC(0));
-        else if (ekind == 0 && eks && g.modeA == 0 && g.modeB == 0) launch(bm_c, bn_c, IC(0), IC(0), IC(0), IC(1));
-        else return -31;
-        return 0;
-    };
-    auto launch_plain = [&](auto bm_c, auto bn_c) {
-        if (g.modeA == 0 && g.modeB == 0) launch(bm_c, bn_c, IC(0), IC(0), IC(0), IC(0));
-        else if (g.modeA == 0) launch(bm_c, bn_c, IC(0), IC(1), IC(0), IC(0));
-        else if (g.modeB == 0) launch(bm_c, bn_c, IC(1), IC(0), IC(0), IC(0));
-        else launch(bm_c, bn_c, IC(1), IC(1), IC(0), IC(0));
-    };
-    int lrc = 0;
-    if (p.narrow) {
-        if constexpr (sizeof(T) == 4) {
-            if (eks) return -31;
-            if (ekind != 0) lrc = launch_epi(IC(128), IC(64));
-            else launch_plain(IC(128), IC(64));
-        }
-    } else if (ekind != 0 || eks) {
-        if (p.big) {
-            if constexpr (sizeof(T) == 4) lrc = launch_epi(IC(128), IC(128));
-        } else {
-            lrc = launch_epi(IC(64), IC(64));
-        }
-    } else {
-        if (p.big) {
-            if constexpr (sizeof(T) == 4) launch_plain(IC(128), IC(128));
-        } else {
-            launch_plain(IC(64), IC(64));
-        }
-    }
-#undef IC
+    if (p.narrow && eks) return -31;                 // (the k-scaled loader has a lower-only output: never a narrow plan)
+    const int lrc = launch_gemm<T>({o.bm, o.bn, ekind, eks, !o.whole, 0, g, ep, dim3((unsigned)o.grid_x, (unsigned)o.grid_y, 1),
+                                    alpha, A, B, beta, C, slabs, st, env.lds_extra});
     if (lrc != 0) return lrc;
     if (g.ksplit > 1) {
         const int64_t tot = nb * M * N;
@@ -1293,13 +1331,10 @@ int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam,
     return nsgp_launch_status();
 }
 
-}  // namespace
-
 // ---- SVGP projection GEMMs with fused epilogues (include/nsgp.h, section K6) ---------------------------
-namespace {
 // tile rows of the float64-accumulating projection for a given shape (see tri_gemm_colstats_f64acc_impl)
 static inline int f64acc_tile_rows(int64_t M, int64_t n, int64_t batch) {
-    return cdiv64(M, 128) * cdiv64(n, NSGP_F64ACC_BN) * batch < 512 ? 64 : 128;
+    return cdiv64(M, 128) * cdiv64(n, F64ACC_BN) * batch < 512 ? 64 : 128;
 }
 
 template <typename T>
@@ -1312,12 +1347,10 @@ int tri_gemm_colstats_impl(const T* L, int trans, const T* X, const T* rowvec, i
     ep.kind = 1; ep.rv = rowvec; ep.p0 = part_dot; ep.p1 = part_sq; ep.modeA = trans ? 1 : 0; ep.modeB = 1;
     ep.part_rows = (int)part_rows;
     const int flags = (trans ? NSGP_GEMM_A_UPPER : NSGP_GEMM_A_LOWER) | NSGP_GEMM_NO_SPLITK;
-    int64_t tiles_m = 0;
     if (part_rows > 0) {                                  // the caller's buffers must hold this launch's tile rows
         Plan p = make_plan<T>(M, n, M, batch, flags, !(sizeof(T) == 8));
         if (part_rows < cdiv64(M, p.big ? 128 : 64)) return -12;
     }
-    (void)tiles_m;
     return gemm_impl<T>(M, n, M, T(1), L, trans ? 1 : M, trans ? M : 1, M * M, 0, X, n, 1, M * n, 0, T(0), Y, n, M * n, 0,
                         batch, 1, flags, nullptr, 0, stream, &ep);
 }
@@ -1344,16 +1377,14 @@ int lqbar_impl(const T* A, const T* C, const T* gvar, int64_t batch, int64_t M, 
     return gemm_impl<T>(M, M, n, T(2), A, n, 1, M * n, 0, C, 1, n, M * n, 0, beta, Lqbar, M, M * M, 0, batch, 1,
                         NSGP_GEMM_C_LOWER, ws, wsb, stream, &ep);
 }
-}  // namespace
 
-namespace {
 // A = L^-1-style projection with float64 arithmetic on float32 data (gemm_kernel<double, 128, 64, 16, ..., MIX = 1>):
 // Y[b] = W[b] X[b] (W: float64 lower triangular (M x M); X, Y: float32 (M x n)), plus the column-statistic partials of
 // nsgp_svgp_tri_gemm_colstats (float32; ceil(M / 128) tile rows).
 struct KzxGen { const float *z, *x, *ls, *os; int D; int64_t sx; };   // generated B operand (Epi::kz ...), or null
 
 static inline bool f64acc_whole(const double* W, int64_t M, int64_t n, int bm) {
-    return M % 4 == 0 && (uintptr_t)W % 32 == 0 && M % bm == 0 && n % NSGP_F64ACC_BN == 0 && M % NSGP_F64ACC_BK == 0;
+    return M % 4 == 0 && (uintptr_t)W % 32 == 0 && M % bm == 0 && n % F64ACC_BN == 0 && M % F64ACC_BK == 0;
 }
 
 int tri_gemm_colstats_f64acc_impl(const double* W, const float* X, const float* rowvec, int64_t batch, int64_t M, int64_t n,
@@ -1366,31 +1397,26 @@ int tri_gemm_colstats_f64acc_impl(const double* W, const float* X, const float* 
     if (!W) return -1; if (!X && !kg) return -2; if (batch < 0) return -4; if (M < 0) return -5; if (n < 0) return -6;
     if (!Y) return -7; if (!part_sq) return -9;
     if (batch == 0 || M == 0 || n == 0) return 0;
-    constexpr int BN_ = NSGP_F64ACC_BN, BK_ = NSGP_F64ACC_BK;
+    constexpr int BN_ = F64ACC_BN, BK_ = F64ACC_BK;
     // 128-row tiles, or 64-row tiles when the 128-row grid would not fill one round of the chip (a rank's share of the
     // hidden layer at 4-8 GPUs, n = 512..1024: 128 workgroups of up to 64 K-tiles each were latency-bound, 96 us)
     const int BM_ = f64acc_tile_rows(M, n, batch);
     if (part_rows < cdiv64(M, BM_)) return -10;
-    GemmArgs g{};
-    g.M = M; g.N = n; g.K = M;
-    g.sam = trans ? 1 : M; g.sak = trans ? M : 1; g.sa1 = M * M; g.sa2 = 0;
-    g.sbk = n; g.sbn = 1; g.sb1 = M * n; g.sb2 = 0;
-    g.ldc = n; g.sc1 = M * n; g.sc2 = 0; g.nb2 = 1;
-    g.tiles_m = cdiv64(M, BM_); g.tiles_n = cdiv64(n, BN_);
-    g.ksplit = 1; g.kper = cdiv64(M, 32) * 32; g.slab = 0;
+    const GemmEnv env = gemm_env();
+    GemmArgs g = gemm_geometry(M, n, M, trans ? 1 : M, trans ? M : 1, M * M, 0, n, 1, M * n, 0, n, M * n, 0, 1);
     g.flags = (trans ? NSGP_GEMM_A_UPPER : NSGP_GEMM_A_LOWER) | NSGP_GEMM_NO_SPLITK;
-    g.nbk = (int)batch; g.xcd_chunk = 0; g.xcd_group = 0; g.part_rows = (int)part_rows;
+    g.tiles_m = cdiv64(M, BM_); g.tiles_n = cdiv64(n, BN_);
+    g.ksplit = 1; g.kper = cdiv64(M, 32) * 32;
+    g.nbk = (int)batch; g.part_rows = (int)part_rows;
     g.modeA = trans ? 1 : 0; g.modeB = 1;
     g.vecA = (M % 4 == 0) && ((uintptr_t)W % 32 == 0);
     g.vecB = kg ? 1 : ((n % 4 == 0) && ((uintptr_t)X % (X64 ? 32 : 16) == 0));
     if (g.tiles_m * g.tiles_n > 2147483647LL || batch > 65535) return -24;
-    if (batch > 1) {                                     // tile order across the batch, as in gemm_impl
-        const char* bpe = getenv("NSGP_GEMM_BATCH_PERM");
-        if (!(bpe && bpe[0] == '0'))
-            g.batch_perm = (g.tiles_m * g.tiles_n * batch <= 512) ? 1 : 0;   // (batch-fastest measured slower here: 314 -> 329 us)
-    }
+    // tile order across the batch as in plan_order, by this kernel's own round (two workgroups per CU at either tile height)
+    // and never batch-fastest (measured slower here: 314 -> 329 us)
+    if (batch > 1 && env.batch_perm != '0') g.batch_perm = (g.tiles_m * g.tiles_n * batch <= 512) ? 1 : 0;
     Epi ep{};
-    ep.kind = 1; ep.rv = rowvec; ep.p0 = part_dot; ep.p1 = part_sq; ep.modeA = trans ? 1 : 0; ep.modeB = 1; ep.p64 = p64;
+    ep.kind = 1; ep.rv = rowvec; ep.p0 = part_dot; ep.p1 = part_sq; ep.modeA = g.modeA; ep.modeB = 1; ep.p64 = p64;
     if (kg) {
         if (!kg->z || !kg->x || !kg->ls || !kg->os) return -2;
         if (kg->D < 1 || kg->D > KGEN_DMAX) return -3;
@@ -1398,39 +1424,13 @@ int tri_gemm_colstats_f64acc_impl(const double* W, const float* X, const float* 
         ep.kz = kg->z; ep.kx = kg->x; ep.kls = kg->ls; ep.kos = kg->os; ep.kD = kg->D; ep.kx_sx = kg->sx;
     }
     const bool whole = g.vecA && g.vecB && M % BM_ == 0 && n % BN_ == 0 && M % BK_ == 0;
-    dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)batch, 1);
-    hipStream_t st = (hipStream_t)stream;
-    // the kernel takes its B / C pointers as double* and reinterprets them (MIX = 1)
-    const double* Bp = reinterpret_cast<const double*>(X);
-    double* Cp = reinterpret_cast<double*>(Y);
-    auto go = [&](auto bm_c, auto edge_c, auto mix_c) {
-        constexpr int BMc = decltype(bm_c)::value, EDGEc = decltype(edge_c)::value, MIXc = decltype(mix_c)::value;
-        constexpr size_t lds = 2 * BK_ * ((BMc + Mfma<double>::PAD) + (BN_ + Mfma<double>::PAD)) * sizeof(double);
-        nsgp_opt_in_lds((const void*)gemm_kernel<double, BMc, BN_, BK_, 0, 1, 1, 0, 0, EDGEc, MIXc>, lds);
-        hipLaunchKernelGGL((gemm_kernel<double, BMc, BN_, BK_, 0, 1, 1, 0, 0, EDGEc, MIXc>), grid, dim3(256), lds, st, g, 1.0,
-                           W, Bp, 0.0, Cp, (double*)nullptr, ep);
-    };
-    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-    using B64 = std::integral_constant<int, 64>; using B128 = std::integral_constant<int, 128>;
-    using I3 = std::integral_constant<int, 3>;
-    auto go_t = [&](auto bm_c, auto edge_c) {                 // transposed-A variant (operand contiguous along m)
-        constexpr int BMc = decltype(bm_c)::value, EDGEc = decltype(edge_c)::value;
-        constexpr size_t lds = 2 * BK_ * ((BMc + Mfma<double>::PAD) + (BN_ + Mfma<double>::PAD)) * sizeof(double);
-        nsgp_opt_in_lds((const void*)gemm_kernel<double, BMc, BN_, BK_, 1, 1, 1, 0, 0, EDGEc, 1>, lds);
-        hipLaunchKernelGGL((gemm_kernel<double, BMc, BN_, BK_, 1, 1, 1, 0, 0, EDGEc, 1>), grid, dim3(256), lds, st, g, 1.0,
-                           W, Bp, 0.0, Cp, (double*)nullptr, ep);
-    };
-    if (trans) {
-        if (BM_ == 128) { if (whole) go_t(B128{}, I0{}); else go_t(B128{}, I1{}); }
-        else { if (whole) go_t(B64{}, I0{}); else go_t(B64{}, I1{}); }
-    }
-    else if (X64) {
-        if (BM_ == 128) { if (whole) go(B128{}, I0{}, I3{}); else go(B128{}, I1{}, I3{}); }
-        else { if (whole) go(B64{}, I0{}, I3{}); else go(B64{}, I1{}, I3{}); }
-    }
-    else if (kg) { if (BM_ == 128) go(B128{}, I0{}, I2{}); else go(B64{}, I0{}, I2{}); }
-    else if (BM_ == 128) { if (whole) go(B128{}, I0{}, I1{}); else go(B128{}, I1{}, I1{}); }
-    else { if (whole) go(B64{}, I0{}, I1{}); else go(B64{}, I1{}, I1{}); }
+    // the kernel takes its B / C pointers as double* and reinterprets them (MIX = 1: float32 B and C; 2: B generated;
+    // 3: float64 B)
+    const int lrc = launch_gemm<double>({BM_, BN_, 1, 0, !whole, X64 ? 3 : (kg ? 2 : 1), g, ep,
+                                         dim3((unsigned)(g.tiles_m * g.tiles_n), (unsigned)batch, 1), 1.0, W,
+                                         reinterpret_cast<const double*>(X), 0.0, reinterpret_cast<double*>(Y), nullptr,
+                                         (hipStream_t)stream, env.lds_extra});
+    if (lrc != 0) return lrc;
     return nsgp_launch_status();
 }
 }  // namespace
@@ -1438,7 +1438,7 @@ int tri_gemm_colstats_f64acc_impl(const double* W, const float* X, const float* 
 extern "C" {
 
 #ifdef NSGP_GEMM_STAMPS
-// diagnostic build: where the workgroups of the following GEMM launches write their stamp records (8 x uint64 each)
+// diagnostic build: where the workgroups of the following GEMM launches write their stamp records (16 x uint64 each)
 int nsgp_debug_gemm_stamps(void* buf, uint64_t cap_records) {
     unsigned long long* b = (unsigned long long*)buf;
     unsigned long long c = cap_records;
@@ -1527,7 +1527,6 @@ int nsgp_gemm_f64(int64_t M, int64_t N, int64_t K, double alpha, const double* A
     return gemm_impl<double>(M, N, K, alpha, A, sam, sak, sa1, sa2, B, sbk, sbn, sb1, sb2, beta, C, ldc, sc1, sc2,
                              nb1, nb2, flags, ws, wsb, stream);
 }
-
 
 size_t nsgp_svgp_colstats_tiles(int64_t M, int64_t n, int64_t batch, int elem_size) {
     if (M <= 0 || n <= 0 || batch <= 0) return 0;
