@@ -11,6 +11,84 @@
 
 namespace {
 
+// ---- pieces of the layer's reductions, each written once ("Layer reductions"); V = 16 / sizeof(T) elements per lane
+template <typename T, int V> struct VecOf;
+template <> struct VecOf<float, 4> { using type = float4; };
+template <> struct VecOf<double, 2> { using type = double2; };
+
+// V consecutive elements at p (V > 1: p is 16-byte aligned)
+template <typename T, int V> __device__ __forceinline__ void ld_vec(const T* __restrict__ p, T (&v)[V]) {
+    if constexpr (V == 1) {
+        v[0] = p[0];
+    } else {
+        const typename VecOf<T, V>::type t = *reinterpret_cast<const typename VecOf<T, V>::type*>(p);
+        v[0] = t.x; v[1] = t.y;
+        if constexpr (V == 4) { v[2] = t.z; v[3] = t.w; }
+    }
+}
+template <typename T, int V> __device__ __forceinline__ void st_vec(T* __restrict__ p, const T (&v)[V]) {
+    if constexpr (V == 1) {
+        p[0] = v[0];
+    } else {
+        typename VecOf<T, V>::type t;
+        t.x = v[0]; t.y = v[1];
+        if constexpr (V == 4) { t.z = v[2]; t.w = v[3]; }
+        *reinterpret_cast<typename VecOf<T, V>::type*>(p) = t;
+    }
+}
+
+// sum of the 16 / sizeof(T) products p[v] q[v], left to right (p, q 16-byte aligned)
+template <typename T, int V = 16 / sizeof(T)> __device__ __forceinline__ T dot_vec(const T* p, const T* q) {
+    T a[V], b[V];
+    ld_vec<T, V>(p, a); ld_vec<T, V>(q, b);
+    T s = a[0] * b[0];
+    for (int v = 1; v < V; ++v) s += a[v] * b[v];
+    return s;
+}
+// sum of the 16 / sizeof(T) elements at p, in pairs: (p0 + p1) + (p2 + p3)
+template <typename T, int V = 16 / sizeof(T)> __device__ __forceinline__ T sum_vec(const T* p) {
+    T a[V];
+    ld_vec<T, V>(p, a);
+    if constexpr (V == 4) return (a[0] + a[1]) + (a[2] + a[3]);
+    else return a[0] + a[1];
+}
+
+// a row dot: may the 16-byte walk be taken; the scalar walk (one lane's share); block sum, thread 0 stores (lds: 4 elements)
+template <typename T> __device__ __forceinline__ bool rowdot_vec_ok(const T* row, const T* gb, int64_t n) {
+    return (n % (16 / sizeof(T)) == 0) && ((uintptr_t)row % 16 == 0) && ((uintptr_t)gb % 16 == 0);
+}
+template <typename T> __device__ __forceinline__ T rowdot_scalar(const T* row, const T* gb, int64_t n) {
+    T acc = T(0);
+    for (int64_t j = threadIdx.x; j < n; j += 256) acc += row[j] * gb[j];
+    return acc;
+}
+template <typename T> __device__ __forceinline__ void block_sum_store(T acc, T* lds, T* out, int64_t at) {
+    acc = block_sum_256(acc, lds);
+    if (threadIdx.x == 0) out[at] = acc;
+}
+
+// s[k] = sum over the tile rows t of part[k][b, t, j]: K (batch, tiles, n) planes in ONE walk (K loads in flight per tile row)
+template <typename TP, int K>
+__device__ __forceinline__ void tile_sums(const TP* const (&part)[K], int64_t b, int64_t tiles, int64_t n, int64_t j, TP (&s)[K]) {
+    for (int k = 0; k < K; ++k) s[k] = TP(0);
+    for (int64_t t = 0; t < tiles; ++t)
+        for (int k = 0; k < K; ++k) s[k] += part[k][(b * tiles + t) * n + j];
+}
+// the affine prior mean (gpytorch ConstantMean / LinearMean of models/dgps.py:40-43): sm += sum_d x[b,j,d] w[b,d], summed in TA
+// from 0, then sm += c[b].  x / w / c batch strides may be 0 = shared; w or c may be null.
+template <typename TA, typename T>
+__device__ __forceinline__ void add_affine_mean(TA& sm, int64_t b, int64_t j, const T* x, int64_t sxb, int D, const T* w,
+                                                int64_t swb, const T* c, int64_t scb) {
+    if (w) {
+        const T* xr = x + b * sxb + j * D;
+        const T* wr = w + b * swb;
+        TA mu = TA(0);
+        for (int d = 0; d < D; ++d) mu += (TA)xr[d] * (TA)wr[d];
+        sm += mu;
+    }
+    if (c) sm += (TA)c[b * scb];
+}
+
 // ---- colstats: mean[b,j] = sum_k A m ; var[b,j] = base[b] + sum_k (C^2 - A^2) ------------------
 template <typename T>
 __global__ __launch_bounds__(256) void colstats_kernel(const T* __restrict__ A, const T* __restrict__ C,
@@ -42,8 +120,7 @@ __global__ __launch_bounds__(256) void colstats_kernel(const T* __restrict__ A, 
 }
 
 // ---- colstats from the GEMM epilogues' per-tile-row partial sums ----------------------------------
-// Optional affine prior mean added on the way out (gpytorch ConstantMean / LinearMean of models/dgps.py:40-43):
-//   mean[b,j] += sum_d x[b,j,d] w[b,d] + c[b]   (x / w / c batch strides may be 0 = shared; w or c may be null).
+// Optional affine prior mean added on the way out:  mean[b,j] += sum_d x[b,j,d] w[b,d] + c[b].
 // TP: element type of the partial buffers (float64 partials of the float64-accumulating projections with a float32 layer)
 template <typename T, typename TP = T>
 __global__ void colstats_finalize_kernel(const TP* __restrict__ pdot, const TP* __restrict__ psqA,
@@ -55,21 +132,11 @@ __global__ void colstats_finalize_kernel(const TP* __restrict__ pdot, const TP* 
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= batch * n) return;
     const int64_t b = idx / n, j = idx % n;
-    TP sm = TP(0), sa = TP(0), sc = TP(0);
-    for (int64_t t = 0; t < tiles; ++t) {
-        const int64_t o = (b * tiles + t) * n + j;
-        sm += pdot[o]; sa += psqA[o]; sc += psqC[o];
-    }
-    if (w) {
-        const T* xr = x + b * sxb + j * D;
-        const T* wr = w + b * swb;
-        TP mu = TP(0);
-        for (int d = 0; d < D; ++d) mu += (TP)xr[d] * (TP)wr[d];
-        sm += mu;
-    }
-    if (c) sm += (TP)c[b * scb];
-    mean[idx] = (T)sm;
-    var[idx] = (T)(((TP)base[b] + (TP)base_add) + (sc - sa));
+    TP s[3];                                             // dot, squares of A, squares of C
+    tile_sums({pdot, psqA, psqC}, b, tiles, n, j, s);
+    add_affine_mean(s[0], b, j, x, sxb, D, w, swb, c, scb);
+    mean[idx] = (T)s[0];
+    var[idx] = (T)(((TP)base[b] + (TP)base_add) + (s[2] - s[1]));
 }
 
 // ---- out[b][i] = sum_j A[b][i][j] * g[b][j]  (one workgroup per row; the m-gradient  A gmean) ------
@@ -82,24 +149,11 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const T* __restrict__ A, co
     const T* gb = g + b * n;
     T acc = T(0);
     constexpr int V = 16 / sizeof(T);
-    const bool vec = (n % V == 0) && ((uintptr_t)row % 16 == 0) && ((uintptr_t)gb % 16 == 0);
-    if (vec) {
-        for (int64_t j = (int64_t)threadIdx.x * V; j < n; j += 256 * V) {
-            if constexpr (sizeof(T) == 4) {
-                const float4 a = *reinterpret_cast<const float4*>(row + j);
-                const float4 q = *reinterpret_cast<const float4*>(gb + j);
-                acc += a.x * q.x + a.y * q.y + a.z * q.z + a.w * q.w;
-            } else {
-                const double2 a = *reinterpret_cast<const double2*>(row + j);
-                const double2 q = *reinterpret_cast<const double2*>(gb + j);
-                acc += a.x * q.x + a.y * q.y;
-            }
-        }
-    } else {
-        for (int64_t j = threadIdx.x; j < n; j += 256) acc += row[j] * gb[j];
-    }
-    acc = block_sum_256(acc, lds);
-    if (threadIdx.x == 0) out[b * M + i] = acc;
+    if (rowdot_vec_ok(row, gb, n))
+        for (int64_t j = (int64_t)threadIdx.x * V; j < n; j += 256 * V) acc += dot_vec(row + j, gb + j);
+    else
+        acc = rowdot_scalar(row, gb, n);
+    block_sum_store(acc, lds, out, b * M + i);
 }
 
 // ---- rowdot plus the reductions over the same columns that the layer's adjoint needs anyway:
@@ -108,24 +162,17 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const T* __restrict__ A, co
 //   row  M+1          : out_1     = sum_j g[b,j]                               (constant mean / bias gradient)
 //   rows M+2 .. M+1+D : out_x[d]  = sum_j x[b,j,d] g[b,j]                      (linear-mean weight gradient)
 // out_1 / out_x are per batch, or summed over the batch when the mean parameters are shared (`shared`).
-// sum of q[0..n) by one 256-thread workgroup: 16-byte loads, four of them in flight per lane per trip (block-reduced; lds: 4
-// elements)
+// sum of q[0..n) by one 256-thread workgroup: 16-byte loads, four in flight per lane per trip (block-reduced; lds: 4 elements)
 template <typename T> __device__ __forceinline__ T strided_sum4(const T* __restrict__ q, int64_t n, T* lds) {
     constexpr int V = 16 / sizeof(T);
     T a0 = T(0), a1 = T(0), a2 = T(0), a3 = T(0);
     int64_t j = 0;
     if ((uintptr_t)q % 16 == 0) {
-        auto ld = [&](int64_t at) __attribute__((always_inline)) {
-            T v = T(0);
-            if constexpr (sizeof(T) == 4) { const float4 t = *reinterpret_cast<const float4*>(q + at); v = (t.x + t.y) + (t.z + t.w); }
-            else { const double2 t = *reinterpret_cast<const double2*>(q + at); v = t.x + t.y; }
-            return v;
-        };
         const int64_t step = 256 * V;
         for (j = (int64_t)threadIdx.x * V; j + 3 * step + V <= n; j += 4 * step) {
-            a0 += ld(j); a1 += ld(j + step); a2 += ld(j + 2 * step); a3 += ld(j + 3 * step);
+            a0 += sum_vec(q + j); a1 += sum_vec(q + j + step); a2 += sum_vec(q + j + 2 * step); a3 += sum_vec(q + j + 3 * step);
         }
-        for (; j + V <= n; j += step) a0 += ld(j);
+        for (; j + V <= n; j += step) a0 += sum_vec(q + j);
         // ragged end: elements [n - n % V, n) by the first lanes
         const int64_t tail0 = n - n % V;
         if ((int64_t)threadIdx.x < n - tail0) a1 += q[tail0 + threadIdx.x];
@@ -149,8 +196,7 @@ __global__ __launch_bounds__(256) void rowdot_affine_kernel(const T* __restrict_
         const T* row = A + (b * M + i) * n;
         const T* gb = g + b * n;
         constexpr int V = 16 / sizeof(T);
-        const bool vec = (n % V == 0) && ((uintptr_t)row % 16 == 0) && ((uintptr_t)gb % 16 == 0);
-        if (vec) {
+        if (rowdot_vec_ok(row, gb, n)) {
             // Chunks of 256 lanes x 16 bytes, walked from a start that differs from row to row: rows are n elements apart
             // (160 KB at the headline's last layer, a multiple of the memory channels' interleave), so workgroups that all
             // begin at column 0 march through the SAME channel together.  Eight chunks in flight per lane.
@@ -161,17 +207,7 @@ __global__ __launch_bounds__(256) void rowdot_affine_kernel(const T* __restrict_
                 int64_t c = c0 + t;
                 if (c >= nch) c -= nch;
                 const int64_t j = (c * 256 + threadIdx.x) * V;
-                if (j < n) {
-                    if constexpr (sizeof(T) == 4) {
-                        const float4 a = *reinterpret_cast<const float4*>(row + j);
-                        const float4 q = *reinterpret_cast<const float4*>(gb + j);
-                        dst += a.x * q.x + a.y * q.y + a.z * q.z + a.w * q.w;
-                    } else {
-                        const double2 a = *reinterpret_cast<const double2*>(row + j);
-                        const double2 q = *reinterpret_cast<const double2*>(gb + j);
-                        dst += a.x * q.x + a.y * q.y;
-                    }
-                }
+                if (j < n) dst += dot_vec(row + j, gb + j);
             };
             int64_t t = 0;
             for (; t + 7 < nch; t += 8) {
@@ -181,10 +217,9 @@ __global__ __launch_bounds__(256) void rowdot_affine_kernel(const T* __restrict_
             for (; t < nch; ++t) chunk(t, acc);
             acc = (acc + a1) + (a2 + a3);
         } else {
-            for (int64_t j = threadIdx.x; j < n; j += 256) acc += row[j] * gb[j];
+            acc = rowdot_scalar(row, gb, n);
         }
-        acc = block_sum_256(acc, lds);
-        if (threadIdx.x == 0) out[b * M + i] = acc;
+        block_sum_store(acc, lds, out, b * M + i);
         return;
     }
     const int e = (int)(i - M);
@@ -192,8 +227,7 @@ __global__ __launch_bounds__(256) void rowdot_affine_kernel(const T* __restrict_
         if (!gv) return;
         // (the virtual rows are ONE workgroup each: with a dependent-latency loop of n / 256 scalar loads they, not the M
         // rows of A, set the launch's duration -- 87 of 100 us at n = 40960.  Four independent loads per lane per trip.)
-        const T* q = gv + b * n;
-        acc = strided_sum4(q, n, lds);
+        acc = strided_sum4(gv + b * n, n, lds);
         if (threadIdx.x == 0) out_gv[b] = acc;
         return;
     }
@@ -715,31 +749,6 @@ static int dsvi_obj_bwd_impl(const T* y, const T* mu, const T* v, const T* noise
 constexpr int DIAG_ROWS = 32;            // rows of A per partial (nsgp_svgp_diag_tiles)
 constexpr int DIAG_BWD_COLS = 4096;      // columns of A per workgroup of the backward pass
 
-template <typename T, int V> struct VecOf;
-template <> struct VecOf<float, 4> { using type = float4; };
-template <> struct VecOf<double, 2> { using type = double2; };
-
-// V consecutive elements at p (V > 1: p is 16-byte aligned)
-template <typename T, int V> __device__ __forceinline__ void ld_vec(const T* __restrict__ p, T (&v)[V]) {
-    if constexpr (V == 1) {
-        v[0] = p[0];
-    } else {
-        const typename VecOf<T, V>::type t = *reinterpret_cast<const typename VecOf<T, V>::type*>(p);
-        v[0] = t.x; v[1] = t.y;
-        if constexpr (V == 4) { v[2] = t.z; v[3] = t.w; }
-    }
-}
-template <typename T, int V> __device__ __forceinline__ void st_vec(T* __restrict__ p, const T (&v)[V]) {
-    if constexpr (V == 1) {
-        p[0] = v[0];
-    } else {
-        typename VecOf<T, V>::type t;
-        t.x = v[0]; t.y = v[1];
-        if constexpr (V == 4) { t.z = v[2]; t.w = v[3]; }
-        *reinterpret_cast<typename VecOf<T, V>::type*>(p) = t;
-    }
-}
-
 // part[b,t,j] = sum_{k in tile t} s2m1[b,k] A[b,k,j]^2.  grid (column groups, T, batch); a lane owns V columns, a
 // workgroup DIAG_ROWS rows (tiles past the last row write zeros: every row of the buffer is written).
 template <typename T, int V>
@@ -777,20 +786,12 @@ __global__ void colstats_finalize_diag_kernel(const T* __restrict__ pdot, int64_
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= batch * n) return;
     const int64_t b = idx / n, j = idx % n;
-    T sm = T(0);
-    for (int64_t t = 0; t < tiles; ++t) sm += pdot[(b * tiles + t) * n + j];
-    double q = 0.0;
-    for (int64_t t = 0; t < qtiles; ++t) q += pq[(b * qtiles + t) * n + j];
-    if (w) {
-        const T* xr = x + b * sxb + j * D;
-        const T* wr = w + b * swb;
-        T mu = T(0);
-        for (int d = 0; d < D; ++d) mu += xr[d] * wr[d];
-        sm += mu;
-    }
-    if (c) sm += c[b * scb];
-    mean[idx] = sm;
-    var[idx] = (T)(((double)base[b] + (double)base_add) + q);
+    T sm[1]; double q[1];
+    tile_sums({pdot}, b, tiles, n, j, sm);
+    tile_sums({pq}, b, qtiles, n, j, q);
+    add_affine_mean(sm[0], b, j, x, sxb, D, w, swb, c, scb);
+    mean[idx] = sm[0];
+    var[idx] = (T)(((double)base[b] + (double)base_add) + q[0]);
 }
 
 // Abar = m gmean^T + 2 diag(s2m1) A diag(gvar), and the partial row sums of A gmean and A^2 gvar over DIAG_BWD_COLS columns:
@@ -890,16 +891,22 @@ static int diag_colsq_impl(const T* A, const T* s2m1, int64_t batch, int64_t M, 
     if (batch == 0 || M == 0 || n == 0) return 0;
     constexpr int V = 16 / sizeof(T);
     hipStream_t st = (hipStream_t)stream;
-    if (n % V == 0 && vec_ok<T>(A)) {
-        if (cdiv64(n, 256 * V) > 2147483647LL) return -5;
-        hipLaunchKernelGGL((diag_colsq_kernel<T, V>), dim3((unsigned)cdiv64(n, 256 * V), (unsigned)Tq, (unsigned)batch),
-                           dim3(256), 0, st, A, s2m1, M, n, part);
-    } else {
-        if (cdiv64(n, 256) > 2147483647LL) return -5;
-        hipLaunchKernelGGL((diag_colsq_kernel<T, 1>), dim3((unsigned)cdiv64(n, 256), (unsigned)Tq, (unsigned)batch),
-                           dim3(256), 0, st, A, s2m1, M, n, part);
-    }
+    const bool vec = n % V == 0 && vec_ok<T>(A);
+    const int64_t groups = cdiv64(n, 256 * (vec ? V : 1));
+    if (groups > 2147483647LL) return -5;
+    const dim3 grid((unsigned)groups, (unsigned)Tq, (unsigned)batch);
+    if (vec) hipLaunchKernelGGL((diag_colsq_kernel<T, V>), grid, dim3(256), 0, st, A, s2m1, M, n, part);
+    else hipLaunchKernelGGL((diag_colsq_kernel<T, 1>), grid, dim3(256), 0, st, A, s2m1, M, n, part);
     return nsgp_launch_status();
+}
+
+// the argument checks that the finalize forms with an affine prior mean share (every form numbers them alike)
+template <typename T>
+static int affine_args_status(const T* x, int64_t sxb, int64_t D, const T* w, int64_t swb, int64_t scb, const T* mean,
+                              const T* var) {
+    if (w && !x) return -9; if (sxb < 0) return -10; if (D < 0 || D > NSGP_MAX_DIM || (w && D == 0)) return -11;
+    if (swb < 0) return -13; if (scb < 0) return -15; if (!mean) return -16; if (!var) return -17;
+    return 0;
 }
 
 template <typename T>
@@ -908,8 +915,7 @@ static int finalize_diag_impl(const T* part_dot, int64_t tiles, const double* pa
                               int64_t swb, const T* c, int64_t scb, T* mean, T* var, void* stream) {
     if (!part_dot) return -1; if (tiles < 0) return -2; if (!part_q) return -3; if (qtiles < 0) return -4;
     if (!base) return -5; if (batch < 0) return -7; if (n < 0) return -8;
-    if (w && !x) return -9; if (sxb < 0) return -10; if (D < 0 || D > NSGP_MAX_DIM || (w && D == 0)) return -11;
-    if (swb < 0) return -13; if (scb < 0) return -15; if (!mean) return -16; if (!var) return -17;
+    if (const int rc = affine_args_status(x, sxb, D, w, swb, scb, mean, var)) return rc;
     if (batch * n == 0) return 0;
     if (cdiv64(batch * n, 256) > 2147483647LL) return -8;
     hipLaunchKernelGGL((colstats_finalize_diag_kernel<T>), dim3((unsigned)cdiv64(batch * n, 256)), dim3(256), 0,
@@ -979,12 +985,29 @@ static int finalize_affine_impl(const TP* part_dot, const TP* part_sq_a, const T
                                 int64_t swb, const T* c, int64_t scb, T* mean, T* var, void* stream) {
     if (!part_dot) return -1; if (!part_sq_a) return -2; if (!part_sq_c) return -3; if (!base) return -4;
     if (batch < 0) return -6; if (tiles < 0) return -7; if (n < 0) return -8;
-    if (w && !x) return -9; if (sxb < 0) return -10; if (D < 0 || D > NSGP_MAX_DIM || (w && D == 0)) return -11;
-    if (swb < 0) return -13; if (scb < 0) return -15; if (!mean) return -16; if (!var) return -17;
+    if (const int rc = affine_args_status(x, sxb, D, w, swb, scb, mean, var)) return rc;
     if (batch * n == 0) return 0;
     hipLaunchKernelGGL((colstats_finalize_kernel<T, TP>), dim3((unsigned)cdiv64(batch * n, 256)), dim3(256), 0,
                        (hipStream_t)stream, part_dot, part_sq_a, part_sq_c, base, base_add, batch, tiles, n, x, sxb,
                        (int)D, w, swb, c, scb, mean, var);
+    return nsgp_launch_status();
+}
+
+// the plain form: its own argument numbering, then the affine form without a prior mean
+template <typename T>
+static int finalize_plain_impl(const T* part_dot, const T* part_sq_a, const T* part_sq_c, const T* base, int64_t batch,
+                               int64_t tiles, int64_t n, T* mean, T* var, void* stream) {
+    if (!part_dot) return -1; if (!part_sq_a) return -2; if (!part_sq_c) return -3; if (!base) return -4;
+    if (batch < 0) return -5; if (tiles < 0) return -6; if (n < 0) return -7; if (!mean) return -8; if (!var) return -9;
+    return finalize_affine_impl<T, T>(part_dot, part_sq_a, part_sq_c, base, T(0), batch, tiles, n, nullptr, 0, 0, nullptr, 0,
+                                      nullptr, 0, mean, var, stream);
+}
+
+template <typename T>
+static int rowdot_impl(const T* A, const T* g, int64_t batch, int64_t M, int64_t n, T* out, void* stream) {
+    if (!A) return -1; if (!g) return -2; if (batch < 0) return -3; if (M < 0) return -4; if (n < 0) return -5; if (!out) return -6;
+    if (batch * M == 0) return 0;
+    hipLaunchKernelGGL((rowdot_kernel<T>), dim3((unsigned)M, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, A, g, M, n, out);
     return nsgp_launch_status();
 }
 
@@ -1082,26 +1105,12 @@ int nsgp_kl_whitened_bwd_f64(const double* m, const double* Lq, int64_t batch, i
 int nsgp_svgp_colstats_finalize_f32(const float* part_dot, const float* part_sq_a, const float* part_sq_c,
                                     const float* base, int64_t batch, int64_t tiles, int64_t n, float* mean,
                                     float* var, void* stream) {
-    if (!part_dot) return -1; if (!part_sq_a) return -2; if (!part_sq_c) return -3; if (!base) return -4;
-    if (batch < 0) return -5; if (tiles < 0) return -6; if (n < 0) return -7; if (!mean) return -8; if (!var) return -9;
-    if (batch * n == 0) return 0;
-    hipLaunchKernelGGL((colstats_finalize_kernel<float>), dim3((unsigned)cdiv64(batch * n, 256)), dim3(256), 0,
-                       (hipStream_t)stream, part_dot, part_sq_a, part_sq_c, base, (float)0, batch, tiles, n,
-                       (const float*)nullptr, (int64_t)0, 0, (const float*)nullptr, (int64_t)0, (const float*)nullptr,
-                       (int64_t)0, mean, var);
-    return nsgp_launch_status();
+    return finalize_plain_impl<float>(part_dot, part_sq_a, part_sq_c, base, batch, tiles, n, mean, var, stream);
 }
 int nsgp_svgp_colstats_finalize_f64(const double* part_dot, const double* part_sq_a, const double* part_sq_c,
                                     const double* base, int64_t batch, int64_t tiles, int64_t n, double* mean,
                                     double* var, void* stream) {
-    if (!part_dot) return -1; if (!part_sq_a) return -2; if (!part_sq_c) return -3; if (!base) return -4;
-    if (batch < 0) return -5; if (tiles < 0) return -6; if (n < 0) return -7; if (!mean) return -8; if (!var) return -9;
-    if (batch * n == 0) return 0;
-    hipLaunchKernelGGL((colstats_finalize_kernel<double>), dim3((unsigned)cdiv64(batch * n, 256)), dim3(256), 0,
-                       (hipStream_t)stream, part_dot, part_sq_a, part_sq_c, base, (double)0, batch, tiles, n,
-                       (const double*)nullptr, (int64_t)0, 0, (const double*)nullptr, (int64_t)0, (const double*)nullptr,
-                       (int64_t)0, mean, var);
-    return nsgp_launch_status();
+    return finalize_plain_impl<double>(part_dot, part_sq_a, part_sq_c, base, batch, tiles, n, mean, var, stream);
 }
 int nsgp_svgp_colstats_finalize_affine_f32(const float* part_dot, const float* part_sq_a, const float* part_sq_c,
                                            const float* base, float base_add, int64_t batch, int64_t tiles, int64_t n,
@@ -1140,21 +1149,10 @@ int nsgp_rowdot_affine_f64(const double* A, const double* g, const double* gv, c
                                       stream);
 }
 int nsgp_rowdot_f32(const float* A, const float* g, int64_t batch, int64_t M, int64_t n, float* out, void* stream) {
-    if (!A) return -1; if (!g) return -2; if (batch < 0) return -3; if (M < 0) return -4; if (n < 0) return -5;
-    if (!out) return -6;
-    if (batch * M == 0) return 0;
-    hipLaunchKernelGGL((rowdot_kernel<float>), dim3((unsigned)M, (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
-                       A, g, M, n, out);
-    return nsgp_launch_status();
+    return rowdot_impl<float>(A, g, batch, M, n, out, stream);
 }
-int nsgp_rowdot_f64(const double* A, const double* g, int64_t batch, int64_t M, int64_t n, double* out,
-                    void* stream) {
-    if (!A) return -1; if (!g) return -2; if (batch < 0) return -3; if (M < 0) return -4; if (n < 0) return -5;
-    if (!out) return -6;
-    if (batch * M == 0) return 0;
-    hipLaunchKernelGGL((rowdot_kernel<double>), dim3((unsigned)M, (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
-                       A, g, M, n, out);
-    return nsgp_launch_status();
+int nsgp_rowdot_f64(const double* A, const double* g, int64_t batch, int64_t M, int64_t n, double* out, void* stream) {
+    return rowdot_impl<double>(A, g, batch, M, n, out, stream);
 }
 
 /* mean-field q(u): column statistics, their adjoint, KL (nsgp.svgp.SVGPMeanFieldLayerFn, nsgp.ops.KlMeanFieldTotalFn) */

@@ -695,6 +695,25 @@ def _affine_args(affine, batch, n, ref):
     return x, sxb, D, w, swb, c, scb
 
 
+def _affine_grad_outputs(affine, swb, scb, w, c, batch, D, ref):
+    """(shared, wbar, cbar) of `_affine_args`' operands: shared = 1 when the mean parameters are shared by the batch (their
+    gradients are then summed over it); wbar / cbar are empty, in the shapes of w / c (None where w / c is None)."""
+    shared = int(affine is not None and swb == 0 and scb == 0)
+    if w is not None and c is not None and batch > 1 and (swb == 0) != (scb == 0):
+        raise BackendError('affine prior mean: weights and constant must both be shared or both be per batch')
+    nb = 1 if shared else batch
+    wbar = None if w is None else torch.empty((nb, D), dtype=ref.dtype, device=ref.device)
+    cbar = None if c is None else torch.empty(nb, dtype=ref.dtype, device=ref.device)
+    return shared, wbar, cbar
+
+
+def _w64_operand(W64f, ref, dims, what):
+    """The float64 W of a float32 layer, checked against the layer's (batch, M) and device, contiguous."""
+    if ref.dtype != torch.float32 or W64f.dtype != torch.float64 or W64f.shape != (*dims, dims[1]) or W64f.device != ref.device:
+        raise BackendError(f'{what}: W64f must be the float64 (b,M,M) W of a float32 layer')
+    return _c(W64f)
+
+
 def _kernel_inputs_args(t, ref, what):
     """(Z, x, ls, os) of an RBF kernel whose Kzx a projection evaluates itself -> the four tensors contiguous (os flat) and
     (b, M, n), checked: ref's device and dtype, Z:(b,M,D), x:(n,D) or (b,n,D), ls:(b,D), os:(b,)."""
@@ -899,10 +918,7 @@ def svgp_project(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None, kern
     if W.shape != (batch, M, M) or Lq.shape != (batch, M, M) or m.shape != (batch, M) or base.shape != (batch,):
         raise BackendError('svgp_project: shapes')
     if W64f is not None:
-        if ref.dtype != torch.float32 or W64f.dtype != torch.float64 or W64f.shape != (batch, M, M) \
-                or W64f.device != ref.device:
-            raise BackendError('svgp_project: W64f must be the float64 (b,M,M) W of a float32 layer')
-        W = _c(W64f)
+        W = _w64_operand(W64f, ref, (batch, M), 'svgp_project')
     if Lq64 is not None:
         if W64f is None or not (b64 or i8) or Lq64.dtype != torch.float64 or Lq64.shape != (batch, M, M) or Lq64.device != ref.device:
             raise BackendError('svgp_project: Lq64 must be the float64 (b,M,M) copy of Lq (with W64f and Kzx64 / i8_inputs)')
@@ -967,17 +983,8 @@ def svgp_project_bwd(Lq, m, A, C, gmean, gvar, affine=None):
     mbar = torch.empty_like(m)
     flops = 1.0 * M * M * n * batch
     basebar = torch.empty(batch, dtype=ref.dtype, device=ref.device)
-    wbar = cbar = None
     x, sxb, D, w, swb, c, scb = _affine_args(affine, batch, n, ref)
-    shared = int(affine is not None and swb == 0 and scb == 0)
-    if affine is not None:
-        if w is not None and c is not None and batch > 1 and (swb == 0) != (scb == 0):
-            raise BackendError('affine prior mean: weights and constant must both be shared or both be per batch')
-        nb = 1 if shared else batch
-        if w is not None:
-            wbar = torch.empty((nb, D), dtype=ref.dtype, device=ref.device)
-        if c is not None:
-            cbar = torch.empty(nb, dtype=ref.dtype, device=ref.device)
+    shared, wbar, cbar = _affine_grad_outputs(affine, swb, scb, w, c, batch, D, ref)
     _lib.call(f'nsgp_rowdot_affine_{sfx}', _p(A), _p(gmean), _p(gvar), _p(x) if wbar is not None else None, sxb, D,
               shared, batch, M, n, _p(mbar), _p(basebar), _p(wbar), _p(cbar), st)
     _timed(lambda: _lib.call(f'nsgp_svgp_abar_{sfx}', _p(Lq), _p(C), _p(A), _p(m), _p(gmean), _p(gvar), batch, M, n,
@@ -1018,9 +1025,7 @@ def svgp_project_diag(first, W, s2m1, m, base, base_add=0.0, affine=None, Kzx=No
     if W.shape != (batch, M, M) or s2m1.shape != (batch, M) or m.shape != (batch, M) or base.shape != (batch,):
         raise BackendError('svgp_project_diag: shapes')
     if W64f is not None:
-        if ref.dtype != torch.float32 or W64f.dtype != torch.float64 or W64f.shape != (batch, M, M) or W64f.device != ref.device:
-            raise BackendError('svgp_project_diag: W64f must be the float64 (b,M,M) W of a float32 layer')
-        W = _c(W64f)
+        W = _w64_operand(W64f, ref, (batch, M), 'svgp_project_diag')
     plan = svgp_projection_plan(M, n, batch, ref.dtype, first, 'diag', i8_planes)
     if first == 'kzx_fused' and not svgp_kzx_fusable(W, kin[0], kin[1], n):
         raise BackendError('svgp_project_diag: the generated-Kzx product needs whole tiles (svgp_kzx_fusable)')
@@ -1042,17 +1047,8 @@ def svgp_project_diag_bwd(m, s2m1, A, gmean, gvar, affine=None):
         raise BackendError('svgp_project_diag_bwd: empty A')
     Abar, mbar, tbar = torch.empty_like(A), torch.empty_like(m), torch.empty_like(m)
     basebar = torch.empty(batch, dtype=ref.dtype, device=ref.device)
-    wbar = cbar = None
     x, sxb, D, w, swb, c, scb = _affine_args(affine, batch, n, ref)
-    shared = int(affine is not None and swb == 0 and scb == 0)
-    if affine is not None:
-        if w is not None and c is not None and batch > 1 and (swb == 0) != (scb == 0):
-            raise BackendError('affine prior mean: weights and constant must both be shared or both be per batch')
-        nb = 1 if shared else batch
-        if w is not None:
-            wbar = torch.empty((nb, D), dtype=ref.dtype, device=ref.device)
-        if c is not None:
-            cbar = torch.empty(nb, dtype=ref.dtype, device=ref.device)
+    shared, wbar, cbar = _affine_grad_outputs(affine, swb, scb, w, c, batch, D, ref)
     ws = _ws(_lib.load().nsgp_svgp_diag_bwd_workspace(batch, M, n), ref.device)
     _lib.call(f'nsgp_svgp_diag_bwd_{sfx}', _p(A), _p(m), _p(s2m1), _p(gmean), _p(gvar), batch, M, n, _p(Abar), _p(mbar),
               _p(tbar), _p(ws), ws.numel(), st)

@@ -15,7 +15,7 @@ import torch
 
 from conftest import measured
 from test_svgp_reduction_cases_cpu import (
-    ADAM_CASES, ADAM_STEPS, C_GAUSS, C_KL, COLSTATS_CASES, DTYPES, FIN_BASE_ADD, FIN_BATCH, FIN_D, FINALIZE_CASES, GAUSS_CASES,
+    ADAM_CASES, ADAM_STEPS, C_GAUSS, C_KL, COLSTATS_CASES, DTYPES, FIN_BASE_ADD, FIN_BATCH, FIN_D, FINALIZE_RUNS, GAUSS_CASES,
     KL_CASES, MISC_N, OBJ_CASES, OBJ_MAX_GROUPS, PLAIN_ROWDOT_CASES, ROWDOT_CASES, SAMPLE_CASES, U, colstats_inputs,
     colstats_reference, finalize_inputs, finalize_reference, gauss_blocks, gauss_inputs, gauss_terms, gen, kl_blocks,
     kl_grad_reference, kl_inputs, kl_reference, kl_terms_count, normal32, obj_inputs, obj_reference, obj_terms_count, red_tol,
@@ -384,9 +384,6 @@ def test_colstats_and_backward_are_exact_and_write_nothing_else(ops, case, dt):
     G.check(_cid(case))
     for name, want in R.items():
         assert same(got[name], want), name
-
-
-FINALIZE_RUNS = [(c, dt) for c in FINALIZE_CASES for dt in BOTH if not (c.form == 'p64' and dt == 'f64')]
 
 
 @pytest.mark.parametrize('case,dt', FINALIZE_RUNS, ids=lambda v: v if isinstance(v, str) else _cid(v))

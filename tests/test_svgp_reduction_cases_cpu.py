@@ -358,6 +358,13 @@ def rowdot_inputs(n, batch, M, D, tag):
     return dict(A=ints((batch, M, n), g), g=ints((batch, n), g), gv=ints((batch, n), g), x=ints((batch, n, D), g))
 
 
+def rowdot_real_inputs(n, batch, M, D, tag):
+    """The same operands with seeded normal values: a changed summation order shows in the bits (the layer's bit record)."""
+    g = gen(f'rowdot-real-{n}-{batch}-{M}-{D}-{tag}')
+    return dict(A=normal32((batch, M, n), g), g=normal32((batch, n), g), gv=normal32((batch, n), g),
+                x=normal32((batch, n, D), g))
+
+
 def rowdot_reference(P, shared):
     """out:(b, M), out_gv:(b,), out_1:(nb,), out_x:(nb, D) with nb = 1 when the mean parameters are shared."""
     out = torch.einsum('bmn,bn->bm', P['A'], P['g'])
@@ -381,6 +388,13 @@ def colstats_inputs(case):
     g = gen(f'colstats-{M}-{n}-{b}')
     return dict(A=ints((b, M, n), g), C=ints((b, M, n), g), m=ints((b, M), g), base=ints((b,), g, 0, 8),
                 gmean=ints((b, n), g), gvar=ints((b, n), g))
+
+
+def colstats_real_inputs(case):
+    M, n, b = case
+    g = gen(f'colstats-real-{M}-{n}-{b}')
+    return dict(A=normal32((b, M, n), g), C=normal32((b, M, n), g), m=normal32((b, M), g), base=uniform32((b,), g, 0.5, 2.0),
+                gmean=normal32((b, n), g), gvar=normal32((b, n), g))
 
 
 def colstats_reference(P):
@@ -431,6 +445,23 @@ def finalize_inputs(case):
     return P
 
 
+def finalize_real_inputs(case):
+    """The same operands with seeded real values.  p64: the float64 partials are products of two float32 numbers, so they
+    are no float32 numbers themselves."""
+    b, D = FIN_BATCH, FIN_D
+    g = gen('finalize-real-' + '-'.join(str(f) for f in case))
+    shape = (b, case.tiles, case.n)
+    P = dict(pdot=normal32(shape, g), psqA=uniform32(shape, g, 0.0, 4.0), psqC=uniform32(shape, g, 0.0, 4.0),
+             base=uniform32((b,), g, 0.5, 2.0), x=normal32((b, case.n, D), g))
+    nb = 1 if case.shared else b
+    P['w'] = normal32((nb, D), g) if case.has_w else None
+    P['c'] = normal32((nb,), g) if case.has_c else None
+    if case.form == 'p64':
+        for k in ('pdot', 'psqA', 'psqC'):
+            P[k] = P[k] * uniform32(shape, g, 0.5, 1.5)
+    return P
+
+
 def finalize_reference(case, P):
     mean = P['pdot'].sum(1)
     if P['w'] is not None:
@@ -467,6 +498,107 @@ def sample_reference(P, ns):
     back = lambda q: q.permute(2, 0, 1).contiguous()                           # noqa: E731
     return dict(h=h, h_mag=mean.abs() + (var.sqrt() * P['eps']).abs(), gmean=back(red(P['gh'])), gvar=back(red(t)),
                 gvar_abs=back(red(t.abs())))
+
+
+def sample_real_inputs(case):
+    """sample_inputs with a seeded normal upstream gradient (the layer's bit record)."""
+    P = sample_inputs(case)
+    P['gh'] = normal32(P['gh'].shape, gen('sample-real-' + '-'.join(str(f) for f in case)))
+    return P
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# mean-field column statistics: diag_colsq, colstats_finalize_diag, diag_bwd (bit record only: tests/test_gpu_meanfield.py
+# holds their values to the oracle)
+# ---------------------------------------------------------------------------------------------------------------------------
+# csrc/svgp.hip: rows of A per partial of diag_colsq, columns of A per workgroup of diag_bwd, bytes per lane of the vector forms
+DIAG_ROWS, DIAG_BWD_COLS, VEC_LANE_BYTES = 32, 4096, 16
+DIAG_BATCH = 2
+DIAG_M = (1, 31, 32, 33, 65)
+DIAG_N = (1, 5, 512, 516, 1024, 1028, 4096, 4100, 8195)
+DIAG_OFFS = (None, 'A', 'gmean')
+# off: the operand that starts one element into its buffer ('gmean': the backward pass alone leaves its vector kernel).
+# extra: tile rows of diag_colsq's partial buffer beyond nsgp_svgp_diag_tiles(M) (they must come out as zeros).
+DiagCase = collections.namedtuple('DiagCase', 'M n off extra')
+DiagFinCase = collections.namedtuple('DiagFinCase', 'tiles qtiles n has_w has_c shared')
+
+
+def diag_tiles(M):
+    """csrc/svgp.hip nsgp_svgp_diag_tiles."""
+    return cdiv(M, DIAG_ROWS)
+
+
+def diag_vec(dt):
+    """Elements per lane of the vector forms."""
+    return VEC_LANE_BYTES // (4 if dt == 'f32' else 8)
+
+
+def diag_groups(n, dt, vec):
+    """diag_colsq_kernel: column groups of 256 lanes (grid.x)."""
+    return cdiv(n, 256 * (diag_vec(dt) if vec else 1))
+
+
+def diag_form(case, dt):
+    """The launch form a row reaches: 'vec', 'scalar-n' (n no multiple of the lane's elements), 'scalar-A' (A misaligned:
+    both passes), 'scalar-g' (gmean misaligned: the backward pass only)."""
+    if case.n % diag_vec(dt):
+        return 'scalar-n'
+    return {None: 'vec', 'A': 'scalar-A', 'gmean': 'scalar-g'}[case.off]
+
+
+def _diag_cases():
+    """Every n with every operand offset, every M with every launch form (at n = 516: the vector kernels in both dtypes,
+    n = 8195: the scalar ones), M and the extra tile row rotating; not the cross product."""
+    rows = {DiagCase(DIAG_M[(k + j) % len(DIAG_M)], n, off, (k + j) % 2)
+            for k, n in enumerate(DIAG_N) for j, off in enumerate(DIAG_OFFS)}
+    rows |= {DiagCase(M, n, off, (i + j + q + 1) % 2)
+             for i, M in enumerate(DIAG_M) for q, n in enumerate((516, 8195)) for j, off in enumerate(DIAG_OFFS)}
+    return sorted(rows, key=lambda c: (c.n, c.M, str(c.off), c.extra))
+
+
+# DIAG_CASES_BEGIN
+DIAG_CASES = _diag_cases()
+DIAG_FIN_CASES = [DiagFinCase(t, q, FIN_N[(i + k) % len(FIN_N)], *combo)
+                  for i, (t, q) in enumerate((t, q) for t in (1, 7) for q in (1, 3)) for k, combo in enumerate(_FIN_COMBOS)]
+# DIAG_CASES_END
+
+
+def diag_inputs(case):
+    """A (b, M, n), s2m1 = s^2 - 1 of both signs, m, and the upstream gradients of mean and var."""
+    b, g = DIAG_BATCH, gen('diag-' + '-'.join(str(f) for f in case))
+    return dict(A=normal32((b, case.M, case.n), g), s2m1=uniform32((b, case.M), g, -0.75, 1.25), m=normal32((b, case.M), g),
+                gmean=normal32((b, case.n), g), gvar=normal32((b, case.n), g))
+
+
+def diag_fin_inputs(case):
+    """finalize_inputs' operands with seeded real values; pq: the float64 partials of diag_colsq, of both signs and no
+    float32 numbers."""
+    b, D = FIN_BATCH, FIN_D
+    g = gen('diagfin-' + '-'.join(str(f) for f in case))
+    P = dict(pdot=normal32((b, case.tiles, case.n), g),
+             pq=normal32((b, case.qtiles, case.n), g) * uniform32((b, case.qtiles, case.n), g, 0.5, 1.5),
+             base=uniform32((b,), g, 0.5, 2.0), x=normal32((b, case.n, D), g))
+    nb = 1 if case.shared else b
+    P['w'] = normal32((nb, D), g) if case.has_w else None
+    P['c'] = normal32((nb,), g) if case.has_c else None
+    return P
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the layer reductions' bit record (tools/record_layer_reduction_hashes.py, tests/test_gpu_layer_reduction_bits.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+# the float64 layer has no float64-partials form
+FINALIZE_RUNS = [(c, dt) for c in FINALIZE_CASES for dt in DTYPES if not (c.form == 'p64' and dt == 'f64')]
+# (kind, row of the kind's table, dtype): every row above that feeds an entry point of the layer half of csrc/svgp.hip
+LAYER_BITS_CASES = [(kind, c, dt) for kind, table in (('rowdot_affine', ROWDOT_CASES), ('rowdot', PLAIN_ROWDOT_CASES),
+                                                      ('colstats', COLSTATS_CASES), ('sample', SAMPLE_CASES),
+                                                      ('diag', DIAG_CASES), ('diag_fin', DIAG_FIN_CASES))
+                    for c in table for dt in DTYPES] + [('finalize', c, dt) for c, dt in FINALIZE_RUNS]
+
+
+def layer_bits_id(run):
+    kind, c, dt = run
+    return '-'.join([kind] + [str(f) for f in c] + [dt])
 
 
 # align: 'aligned' all four buffers 16-byte aligned, 'all_off' all start one element in, 'g_off' only the gradient
@@ -632,6 +764,56 @@ def test_colstats_and_finalize_tables_hit_every_boundary():
         assert bool((pre.float().double() != pre).all()), c
 
 
+def test_diag_table_hits_every_boundary():
+    assert {c.M for c in DIAG_CASES} == set(DIAG_M) and {c.n for c in DIAG_CASES} == set(DIAG_N)
+    assert {diag_tiles(M) for M in DIAG_M} >= {1, 2, 3} and {DIAG_ROWS - 1, DIAG_ROWS, DIAG_ROWS + 1, 1} <= set(DIAG_M)
+    assert any(M > 2 * DIAG_ROWS and M % DIAG_ROWS for M in DIAG_M)                     # a ragged third tile
+    forms = ('vec', 'scalar-n', 'scalar-A', 'scalar-g')
+    for dt in DTYPES:
+        V = diag_vec(dt)
+        assert V == {'f32': 4, 'f64': 2}[dt]
+        vec_n = {c.n for c in DIAG_CASES if diag_form(c, dt) == 'vec'}
+        # one column group filled to its last lane, and one lane of the next
+        assert {256 * V, 256 * V + 4} <= vec_n, dt
+        assert diag_groups(256 * V, dt, True) == 1 and diag_groups(256 * V + 4, dt, True) == 2
+        # one chunk of the backward pass filled, one vector of the next; an odd n in its third chunk
+        assert {DIAG_BWD_COLS, DIAG_BWD_COLS + 4} <= vec_n and any(n % 2 and n > 2 * DIAG_BWD_COLS for n in DIAG_N)
+        scalar_n = {c.n for c in DIAG_CASES if diag_form(c, dt) == 'scalar-n'}
+        assert {1, 5, 8195} <= scalar_n and all(n % V for n in scalar_n)
+        assert any(diag_groups(n, dt, False) > 1 for n in scalar_n)
+        for M in DIAG_M:                                  # every M with every launch form
+            assert {diag_form(c, dt) for c in DIAG_CASES if c.M == M} == set(forms), (M, dt)
+        for form in forms:                                # the extra tile row with every launch form
+            assert {c.extra for c in DIAG_CASES if diag_form(c, dt) == form} == {0, 1}, (form, dt)
+        for n in DIAG_N:                                  # every n with every launch form it can reach
+            want = {'scalar-n'} if n % V else set(forms) - {'scalar-n'}
+            assert {diag_form(c, dt) for c in DIAG_CASES if c.n == n} == want, (n, dt)
+    for n in DIAG_N:
+        assert {c.off for c in DIAG_CASES if c.n == n} == set(DIAG_OFFS), n
+    assert len(DIAG_CASES) < len(DIAG_M) * len(DIAG_N) * len(DIAG_OFFS)                 # not the cross product
+    assert {(c.tiles, c.qtiles) for c in DIAG_FIN_CASES} == {(1, 1), (1, 3), (7, 1), (7, 3)}
+    for tq in ((1, 1), (1, 3), (7, 1), (7, 3)):
+        assert {(c.has_w, c.has_c, c.shared) for c in DIAG_FIN_CASES if (c.tiles, c.qtiles) == tq} == set(_FIN_COMBOS), tq
+    assert {c.n for c in DIAG_FIN_CASES} >= set(FIN_N)
+    for c in DIAG_CASES[:3] + DIAG_CASES[-1:]:
+        P = diag_inputs(c)
+        assert P['A'].shape == (DIAG_BATCH, c.M, c.n) and bool((P['s2m1'] < 0).any() or c.M == 1)
+        assert float(P['s2m1'].min()) >= -0.75 and float(P['s2m1'].max()) <= 1.25
+
+
+def test_layer_bit_record_holds_exactly_the_tables_rows():
+    import json
+    import os
+    ids = [layer_bits_id(r) for r in LAYER_BITS_CASES]
+    assert len(set(ids)) == len(ids) == 2 * (len(ROWDOT_CASES) + len(PLAIN_ROWDOT_CASES) + len(COLSTATS_CASES)
+                                             + len(SAMPLE_CASES) + len(DIAG_CASES) + len(DIAG_FIN_CASES)) + len(FINALIZE_RUNS)
+    assert len(FINALIZE_RUNS) == 2 * len(FINALIZE_CASES) - sum(c.form == 'p64' for c in FINALIZE_CASES)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'layer_reduction_hashes.json')) as f:
+        record = json.load(f)['cases']
+    assert sorted(record) == sorted(ids)
+    assert all(record[k] and all(len(h) == 64 for h in record[k].values()) for k in ids)
+
+
 def test_sample_adam_and_misc_tables():
     assert {(c.S, c.n, c.b) for c in SAMPLE_CASES} >= {(1, 1, 1), (4, 77, 2), (3, 256, 1), (2, 257, 3)}
     for S, n, b in ((4, 77, 2), (3, 256, 1), (2, 257, 3)):
@@ -743,3 +925,7 @@ def test_builder_values_are_float32_numbers():
             check(dict(m=m, L=L, Lg=Lg), c.name)
     for c in SAMPLE_CASES:
         check(sample_inputs(c), c)
+        check(sample_real_inputs(c), c)
+    check(rowdot_real_inputs(1000, 2, 3, 3, 'affine'), 'rowdot')
+    check(colstats_real_inputs(COLSTATS_CASES[-1]), 'colstats')
+    check(diag_inputs(DIAG_CASES[0]), 'diag')
