@@ -603,6 +603,19 @@ int nsgp_dsvi_objective_bwd_f64(const double* y, const double* mu, const double*
                                 double ell_scale, int ngroups, const void* const* m, const void* const* Lq,
                                 const int64_t* batch, int64_t M, double kl_scale, const double* gout, double* gmu, double* gv,
                                 double* gnoise, void* const* gm, void* const* gLq, void* ws, size_t wsb, void* stream);
+/* Gauss-Hermite log marginal of a likelihood of one latent value under q(f_si) = N(mu_si, v_si):
+ *   out[s,i] = log(pi^-1/2 sum_k weights[k] p(y_i | mu_si + sqrt(2 v_si) nodes[k])),   k < Q, 1 <= Q <= 64, a log-sum-exp
+ * kind 0: Bernoulli with a probit link, p = Phi((2 y - 1) f), y in {0, 1}; params NULL.
+ * kind 1: Student-t; params = (nu, s2) on the device; log p is its f-dependent part
+ *         -(nu + 1)/2 log1p((y - f)^2 / (nu s2)) - 1/2 log s2 (the caller adds lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi)).
+ * y:(n) mu, v, out:(S,n), nodes, weights:(Q) (numpy.polynomial.hermite.hermgauss), all on the device; S <= 65535.
+ * A NaN in y, mu or v of a point makes that point's out NaN and no other. */
+int nsgp_gh_log_marginal_f32(int kind, const float* y, const float* mu, const float* v, const float* params,
+                             const float* nodes, const float* weights, int64_t Q, int64_t S, int64_t n, float* out,
+                             void* stream);
+int nsgp_gh_log_marginal_f64(int kind, const double* y, const double* mu, const double* v, const double* params,
+                             const double* nodes, const double* weights, int64_t Q, int64_t S, int64_t n, double* out,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Small helpers on the same stream

@@ -364,6 +364,75 @@ __device__ __forceinline__ void gauss_adjoint_at(int64_t idx, const T* __restric
     gv[idx] = T(-0.5) * coef * is2;
 }
 
+// ---- Gauss-Hermite log marginal: log int p(y | f) N(f | mu, v) df ~ log(pi^-1/2 sum_k w_k p(y | mu + sqrt(2 v) t_k)) for a
+// likelihood of one latent value.  KIND 0: Bernoulli with a probit link, log p = log Phi((2 y - 1) f); KIND 1: Student-t with
+// nu degrees of freedom, location f and scale sqrt(s2) -- its f-dependent part -(nu + 1)/2 log1p(r^2 / (nu s2)) - 1/2 log s2,
+// r = y - f (the normaliser lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi) is the caller's).
+constexpr int GH_MAX_Q = 64;
+constexpr int GH_BERNOULLI = 0, GH_STUDENT_T = 1;
+
+template <typename T> __device__ __forceinline__ T t_log1p(T x);
+template <> __device__ __forceinline__ float t_log1p<float>(float x) { return log1pf(x); }
+template <> __device__ __forceinline__ double t_log1p<double>(double x) { return log1p(x); }
+template <typename T> __device__ __forceinline__ T t_erfc(T x);
+template <> __device__ __forceinline__ float t_erfc<float>(float x) { return erfcf(x); }
+template <> __device__ __forceinline__ double t_erfc<double>(double x) { return erfc(x); }
+template <typename T> __device__ __forceinline__ T t_erfcx(T x);     // exp(x^2) erfc(x)
+template <> __device__ __forceinline__ float t_erfcx<float>(float x) { return erfcxf(x); }
+template <> __device__ __forceinline__ double t_erfcx<double>(double x) { return erfcx(x); }
+
+// what a term needs of (nu, s2), worked out once per thread (Bernoulli: nothing)
+template <typename T> struct GhParams { T ia, hnp1, hls2; };             // 1/(nu s2), (nu + 1)/2, 1/2 log s2
+template <typename T, int KIND> __device__ __forceinline__ GhParams<T> gh_params(const T* __restrict__ params) {
+    GhParams<T> P{};
+    if constexpr (KIND == GH_STUDENT_T) {
+        const T nu = params[0], s2 = params[1];
+        P.ia = T(1) / (nu * s2); P.hnp1 = T(0.5) * (nu + T(1)); P.hls2 = T(0.5) * t_log(s2);
+    }
+    return P;
+}
+
+// nodes and weights (the weights times pi^-1/2) into the workgroup's LDS: every lane reads all Q of them per point
+template <typename T>
+__device__ __forceinline__ void gh_stage_rule(const T* __restrict__ nodes, const T* __restrict__ weights, int Q, T* sn, T* sw) {
+    if ((int)threadIdx.x < Q) {
+        sn[threadIdx.x] = nodes[threadIdx.x];
+        sw[threadIdx.x] = weights[threadIdx.x] * T(0.56418958354775628694807945156077);
+    }
+    __syncthreads();
+}
+
+// log p(y | f) at one node.
+// log Phi(z): z <= 0 through the scaled complementary error function, log(erfcx(-z / sqrt 2) / 2) - z^2 / 2, finite and
+// accurate down to the z ~ -29 the nodes reach (erfc itself underflows near z = -13 in float32); z > 0 as
+// log1p(-erfc(z / sqrt 2) / 2).  A NaN z fails `z <= 0` and leaves the second branch as a NaN.
+template <typename T, int KIND>
+__device__ __forceinline__ T gh_term(T y, T f, const GhParams<T>& P) {
+    if constexpr (KIND == GH_BERNOULLI) {
+        const T z = (T(2) * y - T(1)) * f;
+        if (z <= T(0)) return t_log(T(0.5) * t_erfcx(-z * T(0.70710678118654752440084436210485))) - T(0.5) * z * z;
+        return t_log1p(T(-0.5) * t_erfc(z * T(0.70710678118654752440084436210485)));
+    } else {
+        const T r = y - f;
+        return -P.hnp1 * t_log1p(r * r * P.ia) - P.hls2;
+    }
+}
+
+// the Q-node log marginal of one point as a running log-sum-exp (the largest log p so far is factored out: at z ~ -29
+// every p underflows)
+template <typename T, int KIND>
+__device__ __forceinline__ T gh_point_lse(T y, T mu, T v, const GhParams<T>& P, const T* sn, const T* sw, int Q) {
+    const T sd = t_sqrt(T(2) * v);
+    T m = T(0), s = T(0);
+    for (int k = 0; k < Q; ++k) {
+        const T lp = gh_term<T, KIND>(y, mu + sd * sn[k], P);
+        if (k == 0) { m = lp; s = sw[0]; }
+        else if (lp > m) { s = s * t_exp(m - lp) + sw[k]; m = lp; }
+        else s += sw[k] * t_exp(lp - m);                 // (a NaN lp lands here and makes s a NaN)
+    }
+    return m + t_log(s);
+}
+
 // this lane's share of  sum_{j <= i} l_ij^2 + sum_i (m_i^2 - 2 log |l_ii|)  (twice KL(N(m, L L^T) || N(0, I)), plus M) over
 // rows xb, xb + nblk, ... of one (m, L); only the lower triangle is read (no 64-bit div/mod per element)
 template <typename T>
@@ -431,6 +500,19 @@ __global__ void gauss_ell_bwd_kernel(const T* __restrict__ y, const T* __restric
                                      T* __restrict__ gmu, T* __restrict__ gv) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < S * n) gauss_adjoint_at(idx, y, mu, noise, n, gout[(idx / n) * gs] * scale, gmu, gv);
+}
+
+// out[s, i] = log(pi^-1/2 sum_k w_k p(y_i | mu_si + sqrt(2 v_si) t_k)), one lane per point
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void gh_log_marginal_kernel(const T* __restrict__ y, const T* __restrict__ mu,
+                                                              const T* __restrict__ v, const T* __restrict__ params,
+                                                              const T* __restrict__ nodes, const T* __restrict__ weights,
+                                                              int Q, int64_t S, int64_t n, T* __restrict__ out) {
+    __shared__ T sn[GH_MAX_Q], sw[GH_MAX_Q];
+    gh_stage_rule(nodes, weights, Q, sn, sw);
+    const GhParams<T> P = gh_params<T, KIND>(params);
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx < S * n) out[idx] = gh_point_lse<T, KIND>(y[idx % n], mu[idx], v[idx], P, sn, sw, Q);
 }
 
 // part[b * gridDim.x + blk] = block blk's rows of batch element b
@@ -553,6 +635,35 @@ int gauss_bwd_impl(const T* y, const T* mu, const T* v, const T* noise, int64_t 
         hipLaunchKernelGGL((reduce_final_kernel<T>), dim3(1), dim3(256), 0, st, (const T*)ws, S * nblk, (int64_t)1,
                            scale, T(0), gnoise);
     }
+    return nsgp_launch_status();
+}
+
+// Gauss-Hermite log marginal of a likelihood `kind` with Q nodes: argument checks (minus the position) and the launch
+static inline int gh_check(int kind, const void* y, const void* mu, const void* v, const void* params, const void* nodes,
+                           const void* weights, int64_t Q, int64_t S, int64_t n) {
+    if (kind != GH_BERNOULLI && kind != GH_STUDENT_T) return -1;
+    if (!y) return -2; if (!mu) return -3; if (!v) return -4;
+    if ((kind == GH_STUDENT_T) != (params != nullptr)) return -5;
+    if (!nodes) return -6; if (!weights) return -7; if (Q < 1 || Q > GH_MAX_Q) return -8;
+    if (S < 0 || S > 65535) return -9; if (n < 0) return -10;
+    return 0;
+}
+
+template <typename T>
+int gh_log_marginal_impl(int kind, const T* y, const T* mu, const T* v, const T* params, const T* nodes, const T* weights,
+                         int64_t Q, int64_t S, int64_t n, T* out, void* stream) {
+    if (const int rc = gh_check(kind, y, mu, v, params, nodes, weights, Q, S, n)) return rc;
+    if (!out) return -11;
+    if (S == 0 || n == 0) return 0;
+    if (n > 2147483647LL * 256 / S) return -10;          // S n lanes in blocks of 256: the grid's x extent
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)cdiv64(S * n, 256));
+    if (kind == GH_BERNOULLI)
+        hipLaunchKernelGGL((gh_log_marginal_kernel<T, GH_BERNOULLI>), grid, dim3(256), 0, st, y, mu, v, params, nodes, weights,
+                           (int)Q, S, n, out);
+    else
+        hipLaunchKernelGGL((gh_log_marginal_kernel<T, GH_STUDENT_T>), grid, dim3(256), 0, st, y, mu, v, params, nodes, weights,
+                           (int)Q, S, n, out);
     return nsgp_launch_status();
 }
 
@@ -1245,6 +1356,18 @@ int nsgp_kl_whitened_total_bwd_f64(const double* m, const double* Lq, int64_t ba
                                    const double* gout, double* gm, double* gLq, void* stream) {
     if (!gout) return -6;
     return kl_bwd_impl<double>(m, Lq, batch, M, scale, gm, gLq, stream, gout);
+}
+
+/* Gauss-Hermite log marginal of a Bernoulli (kind 0) or Student-t (kind 1) likelihood (nsgp.ops.gh_log_marginal) */
+int nsgp_gh_log_marginal_f32(int kind, const float* y, const float* mu, const float* v, const float* params,
+                             const float* nodes, const float* weights, int64_t Q, int64_t S, int64_t n, float* out,
+                             void* stream) {
+    return gh_log_marginal_impl<float>(kind, y, mu, v, params, nodes, weights, Q, S, n, out, stream);
+}
+int nsgp_gh_log_marginal_f64(int kind, const double* y, const double* mu, const double* v, const double* params,
+                             const double* nodes, const double* weights, int64_t Q, int64_t S, int64_t n, double* out,
+                             void* stream) {
+    return gh_log_marginal_impl<double>(kind, y, mu, v, params, nodes, weights, Q, S, n, out, stream);
 }
 
 size_t nsgp_dsvi_objective_workspace(int64_t S, int64_t n, int64_t M, int64_t total_batch, int elem_size) {

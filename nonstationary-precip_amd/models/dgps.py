@@ -8,7 +8,8 @@ Same surface (reference file:line):
 Reference quirks kept: the hidden layers are ONE tied layer object repeated
 num_layers times, and predict() returns only the last batch's distribution.  Additions (keyword-only,
 defaults reproduce the reference): DeepGP(..., num_inducing=250, tie_layers=True, variational='cholesky');
-variational='mean_field' gives every layer a MeanFieldVariationalDistribution.
+variational='mean_field' gives every layer a MeanFieldVariationalDistribution; likelihood=None keeps GaussianLikelihood(),
+an instance (BernoulliLikelihood(), StudentTLikelihood()) is used as given.
 """
 import torch
 
@@ -57,7 +58,8 @@ class DeepGPHiddenLayer(DeepGPLayer):
 
 
 class DeepGP(_DeepGPBase):
-    def __init__(self, num_layers, train_x_shape, *, num_inducing=250, tie_layers=True, variational='cholesky'):
+    def __init__(self, num_layers, train_x_shape, *, num_inducing=250, tie_layers=True, variational='cholesky',
+                 likelihood=None):
         hidden = DeepGPHiddenLayer(input_dims=train_x_shape[-1], output_dims=num_output_dims,
                                    num_inducing=num_inducing, mean_type='linear', variational=variational)
         last = DeepGPHiddenLayer(input_dims=hidden.output_dims, output_dims=None,
@@ -71,7 +73,7 @@ class DeepGP(_DeepGPBase):
                                 for _ in range(num_layers - 1)]
         self.layers = torch.nn.ModuleList(stack)
         self.last_layer = last
-        self.likelihood = GaussianLikelihood()
+        self.likelihood = GaussianLikelihood() if likelihood is None else likelihood
 
     def forward(self, inputs):
         rep = inputs

@@ -63,6 +63,12 @@ class num_likelihood_samples(_value_context):
     _global_value = 10
 
 
+class num_gauss_hermite_locs(_value_context):
+    """Nodes of the Gauss-Hermite rule a _OneDimensionalLikelihood (Bernoulli, Student-t) is CONSTRUCTED with
+    [gpytorch.settings.num_gauss_hermite_locs recalled]; 1..64, checked at construction."""
+    _global_value = 20
+
+
 class max_cg_iterations(_value_context):
     """Accepted for source compatibility; this build always factors with the GPU Cholesky."""
     _global_value = 1000

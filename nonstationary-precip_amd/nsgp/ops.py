@@ -1160,6 +1160,37 @@ def gauss_ell_total_bwd(y, mu, v, noise, scale, gout, need_noise=True):
     return gauss_ell_bwd(y, mu, v, noise, scale, gout, need_noise, _form='_total')
 
 
+GH_BERNOULLI, GH_STUDENT_T = 0, 1
+GH_MAX_NODES = 64
+
+
+def _gh_args(kind, y, mu, v, params, nodes, weights, what):
+    """Checked operands of the Gauss-Hermite entry points: y:(n,) mu, v:(S,n); params None (Bernoulli) or the two elements
+    (nu, s2) (Student-t); nodes, weights:(Q,) with 1 <= Q <= 64."""
+    if kind not in (GH_BERNOULLI, GH_STUDENT_T):
+        raise BackendError(f'{what}: kind must be 0 (Bernoulli) or 1 (Student-t), got {kind!r}')
+    ref = _chk(y, mu, v, params, nodes, weights)
+    y, mu, v, nodes, weights = _c(y), _c(mu), _c(v), _c(nodes), _c(weights)
+    if mu.dim() != 2 or y.shape != (mu.shape[1],) or v.shape != mu.shape:
+        raise BackendError(f'{what}: shapes')
+    if nodes.dim() != 1 or weights.shape != nodes.shape or not 1 <= nodes.numel() <= GH_MAX_NODES:
+        raise BackendError(f'{what}: nodes, weights must be (Q,) with 1 <= Q <= {GH_MAX_NODES}, got {tuple(nodes.shape)}, '
+                           f'{tuple(weights.shape)}')
+    if (kind == GH_STUDENT_T) != (params is not None) or (params is not None and params.numel() != 2):
+        raise BackendError(f'{what}: params is (nu, s2) for Student-t and None for Bernoulli')
+    return ref, y, mu, v, (None if params is None else _c(params).reshape(2)), nodes, weights
+
+
+def gh_log_marginal(kind, y, mu, v, params, nodes, weights):
+    """out[s,i] = log(pi^-1/2 sum_k w_k p(y_i | mu_si + sqrt(2 v_si) t_k)), a log-sum-exp per point: nsgp_gh_log_marginal."""
+    ref, y, mu, v, params, nodes, weights = _gh_args(kind, y, mu, v, params, nodes, weights, 'gh_log_marginal')
+    S, n = mu.shape
+    out = torch.empty_like(mu)
+    _lib.call(f'nsgp_gh_log_marginal_{_sfx(ref)}', int(kind), _p(y), _p(mu), _p(v), _p(params), _p(nodes), _p(weights),
+              nodes.numel(), S, n, _p(out), _stream())
+    return out
+
+
 def _kl_whitened_args(m, Lq, what):
     ref = _chk(m, Lq)
     m2, L2 = _c(m), _c(Lq)
