@@ -198,6 +198,19 @@ int nsgp_gemm_f32(int64_t M, int64_t N, int64_t K, float alpha,
                   const float* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2,
                   float beta, float* C, int64_t ldc, int64_t sc1, int64_t sc2,
                   int64_t nb1, int64_t nb2, int flags, void* ws, size_t ws_bytes, void* stream);
+/* nsgp_gemm_f32 that also leaves a float64 copy of C: every element the call writes to C -- the zeros of a C_LOWER output
+ * included -- is written, widened (exactly), to C64[b1*sc64_1 + b2*sc64_2 + row*ldc64 + col]; no other element of C64 is
+ * touched.  The copy comes out of the split-K reduce, which holds the final value in a register, so it costs no pass of its
+ * own -- and exists only when the plan splits along K (nsgp_gemm_plan, out[2] > 1).  A product that is not split returns
+ * NSGP_GEMM_OUT64_UNSPLIT with nothing launched: the caller runs nsgp_gemm_f32 and widens C itself.
+ * Returns -26 for a null C64, -27 for ldc64 < N, otherwise as nsgp_gemm_f32. */
+#define NSGP_GEMM_OUT64_UNSPLIT (-64)
+int nsgp_gemm_f32_out64(int64_t M, int64_t N, int64_t K, float alpha,
+                        const float* A, int64_t sam, int64_t sak, int64_t sa1, int64_t sa2,
+                        const float* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2,
+                        float beta, float* C, int64_t ldc, int64_t sc1, int64_t sc2,
+                        int64_t nb1, int64_t nb2, int flags, void* ws, size_t ws_bytes, void* stream,
+                        double* C64, int64_t ldc64, int64_t sc64_1, int64_t sc64_2);
 int nsgp_gemm_f64(int64_t M, int64_t N, int64_t K, double alpha,
                   const double* A, int64_t sam, int64_t sak, int64_t sa1, int64_t sa2,
                   const double* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2,

@@ -1006,10 +1006,15 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
     NSGP_STAMP_FLUSH();
 }
 
-// C = alpha * sum_s slab[s] + beta * C   (fixed summation order)
+// A float64 copy of what the split-K reduce writes (nsgp_gemm_f32_out64; p == null: none): element (b1, b2, row, col) at
+// p[b1 * s1 + b2 * s2 + row * ld + col].
+struct Out64 { double* p; int64_t ld, s1, s2; };
+
+// C = alpha * sum_s slab[s] + beta * C   (fixed summation order).  One thread per element: the path of every output the
+// vector kernel below does not take.
 template <typename T>
 __global__ void splitk_reduce_kernel(GemmArgs g, T alpha, const T* __restrict__ slabs, T beta, T* __restrict__ C,
-                                     int64_t nb) {
+                                     int64_t nb, Out64 o) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t per = g.M * g.N;
     if (idx >= nb * per) return;
@@ -1017,8 +1022,12 @@ __global__ void splitk_reduce_kernel(GemmArgs g, T alpha, const T* __restrict__ 
     const int64_t row = e / g.N, col = e % g.N;
     const int64_t b1 = bb / g.nb2, b2 = bb % g.nb2;
     T* c = C + b1 * g.sc1 + b2 * g.sc2 + row * g.ldc + col;
+    double* c64 = o.p ? o.p + b1 * o.s1 + b2 * o.s2 + row * o.ld + col : nullptr;
     if ((g.flags & NSGP_GEMM_C_LOWER) && col > row) {
-        if (beta == T(0)) *c = T(0);
+        if (beta == T(0)) {
+            *c = T(0);
+            if (c64) *c64 = 0.0;
+        }
         return;
     }
     T s = T(0);
@@ -1027,6 +1036,125 @@ __global__ void splitk_reduce_kernel(GemmArgs g, T alpha, const T* __restrict__ 
     if ((g.flags & NSGP_GEMM_C_HALFDIAG) && row == col) s *= T(0.5);
     if (beta != T(0)) s += beta * *c;
     *c = s;
+    if (c64) *c64 = (double)s;
+}
+
+// The same reduce, four consecutive columns of one row per thread: 16-byte accesses, 32-bit index arithmetic, the slab loads
+// of a thread in flight together (groups of REDUCE_UNROLL).  Per element the arithmetic is the scalar kernel's, statement for
+// statement, so the bits are too.  The host takes this path when N % 4 == 0, every base and stride is vector-aligned and
+// nb * M * N < 2^31 (reduce_vec_ok); blockIdx.y is the batch element.
+//   not C_LOWER: thread t of a matrix owns group (t / n4, t % n4), n4 = N / 4.
+//   C_LOWER (M == N): threads exist only for the groups with col0 <= row.  Row r has r / 4 + 1 of them, so rows r and
+//     M - 1 - r have n4 + 1 together: thread t < M / 2 * (n4 + 1) owns entry (t / (n4 + 1), t % (n4 + 1)) of that folded
+//     rectangle.  The group the diagonal cuts goes element by element -- col > row is zeroed when beta == 0, left alone
+//     otherwise, and its slab elements are never read.  The groups wholly above the diagonal, which the scalar kernel zeroes
+//     when beta == 0, are a second index range of the same launch that only stores (`fill` groups, folded the same way:
+//     rows r and M - 1 - r have n4 - 1 of them together).
+struct ReduceVec {
+    unsigned M, N, n4, nb2;
+    unsigned groups;              // per matrix: M * n4, or the M / 2 * (n4 + 1) groups of the lower triangle
+    unsigned fill;                // per matrix: groups wholly above the diagonal to zero (C_LOWER and beta == 0), else 0
+    int ksplit, flags;
+    int64_t slab, ldc, sc1, sc2;
+};
+constexpr int REDUCE_UNROLL = 8;
+
+static_assert(REDUCE_UNROLL == 8, "splitk_reduce_vec_kernel spells out the remainders 1..7");
+
+// s += slab[0]; ...; s += slab[CNT - 1] for a thread's vector, every load issued before the first addition
+template <int CNT, typename V, typename T>
+__device__ __forceinline__ void reduce_add(V& s, const T* p, int64_t slab) {
+    V v[CNT];
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) v[i] = *reinterpret_cast<const V*>(p + i * slab);
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) s += v[i];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(ReduceVec r, T alpha, const T* __restrict__ slabs, T beta,
+                                                                T* __restrict__ C, Out64 o) {
+    typedef T V __attribute__((ext_vector_type(4)));
+    typedef double D2 __attribute__((ext_vector_type(2)));
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    const unsigned bb = blockIdx.y;
+    const unsigned b1 = bb / r.nb2, b2 = bb - b1 * r.nb2;
+    const bool cL = (r.flags & NSGP_GEMM_C_LOWER) != 0;
+    unsigned row, cg;
+    bool fill = false;
+    if (t < r.groups) {
+        if (!cL) {
+            row = t / r.n4; cg = t - row * r.n4;
+        } else {
+            const unsigned w = r.n4 + 1, fr = t / w, j = t - fr * w, q = fr >> 2;
+            if (j <= q) { row = fr; cg = j; } else { row = r.M - 1 - fr; cg = j - (q + 1); }
+        }
+    } else {
+        const unsigned u = t - r.groups;
+        if (u >= r.fill) return;
+        const unsigned w = r.n4 - 1, fr = u / w, j = u - fr * w, q = fr >> 2, nup = w - q;
+        if (j < nup) { row = fr; cg = q + 1 + j; } else { row = r.M - 1 - fr; cg = ((r.M - 1 - fr) >> 2) + 1 + (j - nup); }
+        fill = true;
+    }
+    const unsigned col0 = 4 * cg;
+    T* c = C + ((int64_t)b1 * r.sc1 + (int64_t)b2 * r.sc2 + (int64_t)row * r.ldc + col0);
+    double* c64 = o.p ? o.p + ((int64_t)b1 * o.s1 + (int64_t)b2 * o.s2 + (int64_t)row * o.ld + col0) : nullptr;
+    if (fill) {
+        *reinterpret_cast<V*>(c) = V(T(0));
+        if (c64) {
+            reinterpret_cast<D2*>(c64)[0] = D2(0.0);
+            reinterpret_cast<D2*>(c64)[1] = D2(0.0);
+        }
+        return;
+    }
+    const T* p = slabs + ((bb * r.M + row) * r.N + col0);      // < nb * M * N < 2^31
+    const bool half = (r.flags & NSGP_GEMM_C_HALFDIAG) != 0;
+    if (cL && col0 + 3 > row) {                                // the diagonal cuts this group
+        for (unsigned i = 0; i < 4; ++i) {
+            const unsigned col = col0 + i;
+            if (col > row) {
+                if (beta == T(0)) {
+                    c[i] = T(0);
+                    if (c64) c64[i] = 0.0;
+                }
+                continue;
+            }
+            T s = T(0);
+            for (int k = 0; k < r.ksplit; ++k) s += p[k * r.slab + i];
+            s *= alpha;
+            if (half && row == col) s *= T(0.5);
+            if (beta != T(0)) s += beta * c[i];
+            c[i] = s;
+            if (c64) c64[i] = (double)s;
+        }
+        return;
+    }
+    V s = V(T(0));
+    int k = 0;
+    for (; k + REDUCE_UNROLL <= r.ksplit; k += REDUCE_UNROLL, p += REDUCE_UNROLL * r.slab)
+        reduce_add<REDUCE_UNROLL, V>(s, p, r.slab);
+    switch (r.ksplit - k) {                                    // the remainder, its loads in flight together too
+        case 1: reduce_add<1, V>(s, p, r.slab); break;
+        case 2: reduce_add<2, V>(s, p, r.slab); break;
+        case 3: reduce_add<3, V>(s, p, r.slab); break;
+        case 4: reduce_add<4, V>(s, p, r.slab); break;
+        case 5: reduce_add<5, V>(s, p, r.slab); break;
+        case 6: reduce_add<6, V>(s, p, r.slab); break;
+        case 7: reduce_add<7, V>(s, p, r.slab); break;
+        default: break;
+    }
+    s *= alpha;
+    if (half && (row >> 2) == cg) {                            // (not C_LOWER: the diagonal element of a whole group)
+        const unsigned d = row & 3;
+        s.x = d == 0 ? s.x * T(0.5) : s.x; s.y = d == 1 ? s.y * T(0.5) : s.y;
+        s.z = d == 2 ? s.z * T(0.5) : s.z; s.w = d == 3 ? s.w * T(0.5) : s.w;
+    }
+    if (beta != T(0)) s += beta * *reinterpret_cast<const V*>(c);
+    *reinterpret_cast<V*>(c) = s;
+    if (c64) {
+        reinterpret_cast<D2*>(c64)[0] = D2{(double)s.x, (double)s.y};
+        reinterpret_cast<D2*>(c64)[1] = D2{(double)s.z, (double)s.w};
+    }
 }
 
 struct Plan { int big, narrow; int64_t ksplit, kper; };
@@ -1263,13 +1391,49 @@ static inline GemmArgs gemm_geometry(int64_t M, int64_t N, int64_t K, int64_t sa
     return g;
 }
 
+// The reduce of a split launch: the vector kernel where its accesses are aligned and its indices fit 32 bits, else the
+// scalar one (see splitk_reduce_vec_kernel; a C_LOWER output also has to be square there).
+template <typename T>
+static inline bool reduce_vec_ok(const GemmArgs& g, const T* slabs, const T* C, int64_t nb, int64_t nb1, const Out64& o) {
+    const size_t al = 4 * sizeof(T);
+    auto s_ok = [&](int64_t s1, int64_t s2, int64_t q) { return (nb1 == 1 || s1 % q == 0) && (g.nb2 == 1 || s2 % q == 0); };
+    if (g.N % 4 != 0 || nb * g.M * g.N >= 2147483648LL || nb > 65535) return false;
+    if ((uintptr_t)slabs % al || (uintptr_t)C % al || g.ldc % 4 || !s_ok(g.sc1, g.sc2, 4)) return false;
+    if ((g.flags & NSGP_GEMM_C_LOWER) && g.M != g.N) return false;
+    if (o.p && ((uintptr_t)o.p % 16 || o.ld % 2 || !s_ok(o.s1, o.s2, 2))) return false;
+    return true;
+}
+
+template <typename T>
+static void launch_reduce(const GemmArgs& g, T alpha, const T* slabs, T beta, T* C, int64_t nb, int64_t nb1, const Out64& o,
+                          hipStream_t st) {
+    if (!reduce_vec_ok<T>(g, slabs, C, nb, nb1, o)) {
+        hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)cdiv64(nb * g.M * g.N, 256)), dim3(256), 0, st, g, alpha,
+                           slabs, beta, C, nb, o);
+        return;
+    }
+    ReduceVec r{};
+    r.M = (unsigned)g.M; r.N = (unsigned)g.N; r.n4 = (unsigned)(g.N / 4); r.nb2 = (unsigned)g.nb2;
+    r.ksplit = (int)g.ksplit; r.flags = g.flags;
+    r.slab = g.slab; r.ldc = g.ldc; r.sc1 = g.sc1; r.sc2 = g.sc2;
+    if (g.flags & NSGP_GEMM_C_LOWER) {
+        r.groups = r.M / 2 * (r.n4 + 1);
+        r.fill = beta == T(0) ? r.M / 2 * (r.n4 - 1) : 0;
+    } else {
+        r.groups = r.M * r.n4;
+    }
+    hipLaunchKernelGGL((splitk_reduce_vec_kernel<T>), dim3((r.groups + r.fill + 255) / 256, (unsigned)nb), dim3(256), 0, st, r,
+                       alpha, slabs, beta, C, o);
+}
+
 template <typename T>
 int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam, int64_t sak, int64_t sa1,
               int64_t sa2, const T* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2, T beta, T* C,
               int64_t ldc, int64_t sc1, int64_t sc2, int64_t nb1, int64_t nb2, int flags, void* ws, size_t wsb,
-              void* stream, const Epi* epi = nullptr) {
+              void* stream, const Epi* epi = nullptr, const Out64* o64 = nullptr) {
     if (M < 0) return -1; if (N < 0) return -2; if (K < 0) return -3;
     if (nb1 < 1 || nb2 < 1) return -20;
+    if (o64 && !o64->p) return -26; if (o64 && o64->ld < N) return -27;
     if (M == 0 || N == 0) return 0;
     if (!A && K > 0) return -5; if (!B && K > 0) return -10; if (!C) return -16; if (ldc < N) return -17;
     if ((flags & NSGP_GEMM_A_LOWER) && (flags & NSGP_GEMM_A_UPPER)) return -22;
@@ -1278,6 +1442,7 @@ int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam,
     const bool has_epi = epi && (epi->kind != 0 || epi->ks);
     const GemmEnv env = gemm_env();
     Plan p = make_plan<T>(M, N, K, nb, flags, !(has_epi && sizeof(T) == 8), env);   // fused variants: f64 on 64-tiles only
+    if (o64 && p.ksplit == 1) return NSGP_GEMM_OUT64_UNSPLIT;     // nothing launched: only the reduce writes the copy
     GemmArgs g = gemm_geometry(M, N, K, sam, sak, sa1, sa2, sbk, sbn, sb1, sb2, ldc, sc1, sc2, nb2);
     g.ksplit = p.ksplit; g.kper = p.kper; g.slab = nb * M * N; g.flags = flags;
     g.modeA = (sak == 1) ? 0 : (sam == 1 ? 1 : 0);
@@ -1323,11 +1488,7 @@ int gemm_impl(int64_t M, int64_t N, int64_t K, T alpha, const T* A, int64_t sam,
     const int lrc = launch_gemm<T>({o.bm, o.bn, ekind, eks, !o.whole, 0, g, ep, dim3((unsigned)o.grid_x, (unsigned)o.grid_y, 1),
                                     alpha, A, B, beta, C, slabs, st, env.lds_extra});
     if (lrc != 0) return lrc;
-    if (g.ksplit > 1) {
-        const int64_t tot = nb * M * N;
-        hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)cdiv64(tot, 256)), dim3(256), 0, st, g, alpha,
-                           (const T*)slabs, beta, C, nb);
-    }
+    if (g.ksplit > 1) launch_reduce<T>(g, alpha, slabs, beta, C, nb, nb1, o64 ? *o64 : Out64{}, st);
     return nsgp_launch_status();
 }
 
@@ -1519,6 +1680,14 @@ int nsgp_gemm_f32(int64_t M, int64_t N, int64_t K, float alpha, const float* A, 
                   void* ws, size_t wsb, void* stream) {
     return gemm_impl<float>(M, N, K, alpha, A, sam, sak, sa1, sa2, B, sbk, sbn, sb1, sb2, beta, C, ldc, sc1, sc2,
                             nb1, nb2, flags, ws, wsb, stream);
+}
+int nsgp_gemm_f32_out64(int64_t M, int64_t N, int64_t K, float alpha, const float* A, int64_t sam, int64_t sak,
+                        int64_t sa1, int64_t sa2, const float* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2,
+                        float beta, float* C, int64_t ldc, int64_t sc1, int64_t sc2, int64_t nb1, int64_t nb2, int flags,
+                        void* ws, size_t wsb, void* stream, double* C64, int64_t ldc64, int64_t sc64_1, int64_t sc64_2) {
+    const Out64 o{C64, ldc64, sc64_1, sc64_2};
+    return gemm_impl<float>(M, N, K, alpha, A, sam, sak, sa1, sa2, B, sbk, sbn, sb1, sb2, beta, C, ldc, sc1, sc2,
+                            nb1, nb2, flags, ws, wsb, stream, nullptr, &o);
 }
 int nsgp_gemm_f64(int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t sam, int64_t sak,
                   int64_t sa1, int64_t sa2, const double* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2,

@@ -32,7 +32,8 @@
 // contiguous run in memory, so no registers are spent on staging; NSGP_I8_DMA=0 builds the register-staged form); the K
 // planes of a K-step stay in registers while the W planes stream through; behind the stages, 1.5 KB for the row scales and
 // the row vector of the tile's 128 rows, which the prologue fetches beside the first stage so that the epilogue reads no
-// global memory; two workgroups per CU (2 x 57.5 / 61.5 KB of the 160 KB LDS, 210 / 253 VGPRs, no scratch).
+// global memory, and 2 KB for the column-statistics reduction; two workgroups per CU (2 x 59.5 / 63.5 KB of the 160 KB LDS,
+// 227 / 252 VGPRs, no scratch).  With four planes a workgroup walks two column tiles (i8_walk).
 #include <cstdlib>
 #include "common.h"
 
@@ -42,6 +43,9 @@ namespace {
 #define NSGP_I8_DMA 1
 #endif
 constexpr int I8_BM = 128, I8_BN = 64, I8_BK = 32;
+// column tiles a workgroup of i8_proj_kernel walks: two with four Kzx planes; one with five, whose six level accumulators
+// leave no registers for a loop around the tile (it spills: 6 VGPRs at two tiles)
+constexpr int i8_walk(int sk) { return sk == 4 ? 2 : 1; }
 constexpr int I8_SW = 5;                                    // digit planes of W (K: 4 or 5, template SK; levels a + b < LEV)
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -176,6 +180,7 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
     unsigned char* Bs = i8_smem + 2 * A_STAGE;              // [2][B_STAGE]
     double* Ws = reinterpret_cast<double*>(i8_smem + 2 * (A_STAGE + B_STAGE));           // [128] wsc of the tile's rows
     float* Rs = reinterpret_cast<float*>(Ws + I8_BM);                                     // [128] rv of the tile's rows
+    double* red = reinterpret_cast<double*>(Rs + I8_BM);    // [2 quantities][2 wave rows][64 columns] of the epilogue
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 32;
     const int64_t bb = blockIdx.y;
@@ -189,14 +194,21 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
     // as it was: one K-block of prefetch, vmcnt(0) and a barrier per K-block, 28 KB into LDS per 112 MFMAs (2.6 GB per
     // launch, 7.4 TB/s).  Not built: a ring of three stages with counted waits (W alone fits three stages twice per CU, 2 x
     // 61.5 KB, if the Kzx fragments go straight to registers -- whose ordinary loads the compiler waits for with vmcnt(0)
-    // while an LDS-DMA is in flight, so they would have to be issued and counted by hand), and more than one tile per
-    // workgroup.
+    // while an LDS-DMA is in flight, so they would have to be issued and counted by hand).
+    // Two column tiles per workgroup (below): 289.4 -> 279.4 us for <0,4,5>; four tiles: 293.2 (too few workgroups for the
+    // tail); <.,5,6> spills under a tile loop and keeps one tile (profiles/splitk_reduce_i8_walk/).
     // (Tried and dropped: an XCD-grouped order -- workgroup 8 q + x, which the hardware places on XCD x, walking all row tiles of
     // column tiles x, x + 8, ... back to back so that a column tile's Kzx planes enter that L2 once: 0.441 -> 0.534 ms per
     // headline step, like the same experiment on the float32 GEMM.)
-    const int bm = tiles_m - 1 - (int)blockIdx.x / tiles_n;          // long K ranges first
-    const int bn = (int)blockIdx.x % tiles_n;
-    const int64_t m0 = (int64_t)bm * I8_BM, n0 = (int64_t)bn * I8_BN;
+    // A workgroup walks up to TW consecutive column tiles of one tile row: same W blocks, same K range, and the first
+    // stage and digit-scale slots of tile t + 1 are issued before the epilogue of tile t, so that only the first tile of a
+    // walk pays the cold latency of its prologue in the open (the row scales and the row vector are the walk's).
+    constexpr int TW = i8_walk(SK);
+    const int walks_n = (tiles_n + TW - 1) / TW;
+    const int bm = tiles_m - 1 - (int)blockIdx.x / walks_n;          // long K ranges first
+    const int bn0 = ((int)blockIdx.x % walks_n) * TW;
+    const int ntile = TW == 1 ? 1 : __builtin_amdgcn_readfirstlane(tiles_n - bn0 < TW ? tiles_n - bn0 : TW);
+    const int64_t m0 = (int64_t)bm * I8_BM, n00 = (int64_t)bn0 * I8_BN;
     int nkb = (int)((m0 + I8_BM) / I8_BK);                  // lower triangular W: k < m0 + 128
     if (nkb > KB) nkb = (int)KB;
     const signed char* Wb = Wd + bb * (int64_t)I8_SW * KB * 2 * Mp * 16;
@@ -204,24 +216,31 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
     const int64_t wplane = KB * 2 * Mp * 16, kplane = KB * 2 * np * 16;
 
     // staging: piece q of A = (plane a, half h, row) = q / 256, (q % 256) / 128, q % 128; LDS offset 16 q.  5 per thread.
-    const signed char* ga[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int q = tid + 256 * j;
-        const int a = q >> 8, h = (q >> 7) & 1, row = q & 127;
-        ga[j] = Wb + a * wplane + (int64_t)h * Mp * 16 + (m0 + row) * 16;
-    }
     // piece q of B = (plane s, half h, col) = q / 128, (q % 128) / 64, q % 64: SK x 128 pieces, NPB per thread (the last
-    // one of 5 planes only for the first 128 threads)
+    // one of 5 planes only for the first 128 threads).
+    // The addresses are those of column tile t of the walk, worked out again from the thread index wherever a tile needs
+    // them -- through a value the compiler cannot see through: pointers kept from one tile to the next would stay in
+    // registers across the epilogue, which has none to spare.
     constexpr int NPB = (SK * 128 + 255) / 256;
+    const signed char* ga[5];
     const signed char* gb[NPB];
+    auto pieces = [&](int t) __attribute__((always_inline)) {
+        int tv = tid;
+        asm volatile("" : "+v"(tv));
 #pragma unroll
-    for (int j = 0; j < NPB; ++j) {
-        int q = tid + 256 * j;
-        if (q >= SK * 128) q = SK * 128 - 1;                       // (clamped: loaded twice, stored once)
-        const int s = q >> 7, h = (q >> 6) & 1, col = q & 63;
-        gb[j] = Kb + s * kplane + (int64_t)h * np * 16 + (n0 + col) * 16;
-    }
+        for (int j = 0; j < 5; ++j) {
+            const int q = tv + 256 * j;
+            const int a = q >> 8, h = (q >> 7) & 1, row = q & 127;
+            ga[j] = Wb + a * wplane + (int64_t)h * Mp * 16 + (m0 + row) * 16;
+        }
+#pragma unroll
+        for (int j = 0; j < NPB; ++j) {
+            int q = tv + 256 * j;
+            if (q >= SK * 128) q = SK * 128 - 1;                       // (clamped: loaded twice, stored once)
+            const int s = q >> 7, h = (q >> 6) & 1, col = q & 63;
+            gb[j] = Kb + s * kplane + (int64_t)h * np * 16 + (n00 + t * I8_BN + col) * 16;
+        }
+    };
     const int64_t astep = 2 * Mp * 16, bstep = 2 * np * 16;          // bytes per k-block
 #if NSGP_I8_DMA
     // Staging by LDS-DMA (global_load_lds_dwordx4): the digit planes are stored in the order the LDS image wants them, so a
@@ -256,14 +275,6 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
             if (tid + 256 * j < SK * 128) *reinterpret_cast<v4i*>(Bs + buf * B_STAGE + (tid + 256 * j) * 16) = rb[j];
     };
 
-    v16i acc[LEV][2];
-#pragma unroll
-    for (int l = 0; l < LEV; ++l)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[l][i][r] = 0;
-
     // this wave's rows reach k < m0 + wm0 + 64: the upper wave row has nothing to do in the tile's last two k-blocks
     const int wave_nkb = __builtin_amdgcn_readfirstlane((int)((m0 + wm0 + 64 + I8_BK - 1) / I8_BK));
     const int half = lane >> 5, lr = lane & 31;
@@ -272,26 +283,44 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
     // folded by the barrier that publishes the first stage -- the build's slot of k-block 0 for these columns, NaN if the
     // slot of any k-block this tile reads is NaN.
     const int64_t gx = (np + 255) >> 8;
-    const double* ks = ksc + bb * KB * gx + (n0 >> 8);
+    const double* ksb = ksc + bb * KB * gx;
     const float* rvb = rv ? rv + bb * M : nullptr;
+    // the first stage and the digit-scale slots of column tile t of the walk (clamped index, not a branch)
+    auto stage0 = [&](int t) __attribute__((always_inline)) {
+        pieces(t);
 #if NSGP_I8_DMA
-    dma(0, 0);
+        dma(0, 0);
 #else
-    gload(0);
-    sstore(0);
+        gload(0);
+        sstore(0);
 #endif
+        return ksb[((n00 + t * I8_BN) >> 8) + (int64_t)(tid < nkb ? tid : nkb - 1) * gx];
+    };
+    double kslot = stage0(0);
     // (clamped indices, not branches: the three loads leave together and are waited for once, with the stage)
-    const double kslot = ks[(int64_t)(tid < nkb ? tid : nkb - 1) * gx];
     const int64_t prow = m0 + (tid & (I8_BM - 1)), crow = prow < M ? prow : M - 1;
     const double wload = wsc[bb * M + crow];
     const float rload = rvb ? rvb[crow] : 0.0f;
     const double wrow = prow < M ? wload : 0.0;
     const float rrow = prow < M ? rload : 0.0f;
     if (tid < I8_BM) { Ws[tid] = wrow; Rs[tid] = rrow; }
+#pragma unroll 1
+    for (int t = 0; t < ntile; ++t) {
+    const int bn = bn0 + t;
+    const int64_t n0 = (int64_t)bn * I8_BN;
+    const double* ks = ksb + (n0 >> 8);
+    v16i acc[LEV][2];
+#pragma unroll
+    for (int l = 0; l < LEV; ++l)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[l][i][r] = 0;
 #if NSGP_I8_DMA
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the tile's first stage: issued above, or before the last epilogue
 #endif
     const double kscale = __syncthreads_or(kslot != kslot) ? __builtin_nan("") : ks[0];
+    if (t > 0) pieces(t);                                  // (the first tile's are the prologue's)
     for (int kb = 0; kb < nkb; ++kb) {
         const int buf = kb & 1;
 #if NSGP_I8_DMA
@@ -334,17 +363,27 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
         __syncthreads();                                   // ... and so have everybody else's
     }
 
+    // The next tile's first stage goes to buffer 0 now -- every wave is behind the loop's last barrier, and the epilogue's
+    // scratch has LDS of its own -- and lands under the epilogue.
+    if (t + 1 < ntile) kslot = stage0(t + 1);
     // epilogue: levels -> float64 -> one rounding to float32; column statistics from the float64 values.  No global load is
     // left in it: a load under the per-element `in` made the compiler branch around it and wait for it alone, 64 dependent
     // round trips per workgroup.
     double sdot = 0.0, ssq = 0.0;
-    const int64_t col = n0 + wn0 + lr;
+    // (the tile row as a value the compiler cannot see through: it would otherwise compute the 32 row offsets of the stores
+    // once per walk and keep them in registers across the K loop, which the accumulators need)
+    int64_t m0e = m0;
+    asm volatile("" : "+s"(m0e));
+    int lanee = lane, tide = tid;
+    asm volatile("" : "+v"(lanee), "+v"(tide));
+    const int halfe = lanee >> 5, lre = lanee & 31;
+    const int64_t col = n0 + wn0 + lre;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int lrow = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int64_t row = m0 + lrow;
+            const int lrow = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * halfe;
+            const int64_t row = m0e + lrow;
             const double wr = Ws[lrow];
             const float rr = Rs[lrow];
             double v = (double)acc[LEV - 1][i][r];
@@ -358,16 +397,15 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
         }
     sdot += __shfl_xor(sdot, 32, 64);
     ssq += __shfl_xor(ssq, 32, 64);
-    double* red = reinterpret_cast<double*>(i8_smem);       // [2 quantities][2 wave rows][64 columns]
-    __syncthreads();
-    if (lane < 32) {
-        red[(0 + (wave >> 1)) * I8_BN + wn0 + lane] = sdot;
-        red[(2 + (wave >> 1)) * I8_BN + wn0 + lane] = ssq;
+    __syncthreads();                                        // (the last tile's sums have been read)
+    if (lanee < 32) {
+        red[(0 + (wave >> 1)) * I8_BN + wn0 + lanee] = sdot;
+        red[(2 + (wave >> 1)) * I8_BN + wn0 + lanee] = ssq;
     }
     __syncthreads();
-    if (tid < I8_BN && n0 + tid < n) {
-        const int64_t o = (bb * part_rows + bm) * n + n0 + tid;
-        const double d = red[tid] + red[I8_BN + tid], q = red[2 * I8_BN + tid] + red[3 * I8_BN + tid];
+    if (tide < I8_BN && n0 + tide < n) {
+        const int64_t o = (bb * part_rows + bm) * n + n0 + tide;
+        const double d = red[tide] + red[I8_BN + tide], q = red[2 * I8_BN + tide] + red[3 * I8_BN + tide];
         if (P64) {
             if (p0) reinterpret_cast<double*>(p0)[o] = d;
             reinterpret_cast<double*>(p1)[o] = q;
@@ -376,6 +414,7 @@ __global__ __launch_bounds__(256, 2) void i8_proj_kernel(const signed char* __re
             reinterpret_cast<float*>(p1)[o] = (float)q;
         }
     }
+    }   // column tiles of the walk
 }
 
 static inline int64_t i8_mp(int64_t M) { return cdiv64(M, I8_BM) * I8_BM; }
@@ -442,9 +481,10 @@ int nsgp_svgp_tri_gemm_colstats_i8(const void* Wd, const double* wscale, const v
     if (!Y) return -9; if (!part_sq) return -11; if (part_rows < cdiv64(M > 0 ? M : 1, I8_BM)) return -12;
     if (batch == 0 || M == 0 || n == 0) return 0;
     const int64_t Mp = i8_mp(M), np = i8_np(n), KB = i8_kb(M);
-    const int64_t tiles_n = np / I8_BN, tiles = (Mp / I8_BM) * tiles_n;
+    const int64_t tiles_n = np / I8_BN, tiles = (Mp / I8_BM) * cdiv64(tiles_n, i8_walk(planes));   // one workgroup per walk
     if (tiles > 2147483647LL || batch > 65535) return -8;
-    const size_t lds = 2 * (size_t)(I8_SW * 2 * I8_BM * 16 + planes * 2 * I8_BN * 16) + I8_BM * (sizeof(double) + sizeof(float));
+    const size_t lds = 2 * (size_t)(I8_SW * 2 * I8_BM * 16 + planes * 2 * I8_BN * 16) + I8_BM * (sizeof(double) + sizeof(float)) +
+                       4 * I8_BN * sizeof(double);
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)tiles, (unsigned)batch);
 #define NSGP_I8_PROJ(PP, SS) hipLaunchKernelGGL((i8_proj_kernel<PP, SS, (SS == 5 ? 6 : 5)>), grid, dim3(256), lds, st, (const signed char*)Wd, wscale, \

@@ -500,22 +500,40 @@ def gemm_plan(A, B, ta=False, tb=False, flags=0, out=None):
     return GemmPlan(*buf)
 
 
-def gemm(A, B, ta=False, tb=False, alpha=1.0, beta=0.0, out=None, flags=0):
+GEMM_OUT64_UNSPLIT = -64   # NSGP_GEMM_OUT64_UNSPLIT (include/nsgp.h)
+
+
+def gemm(A, B, ta=False, tb=False, alpha=1.0, beta=0.0, out=None, flags=0, out64=None):
     """out = alpha * op(A) @ op(B) + beta * out on the matrix cores.  2-D or batched 3-D operands
-    (a 2-D operand broadcasts against a 3-D one)."""
+    (a 2-D operand broadcasts against a 3-D one).
+    out64 (float32 product): a contiguous float64 tensor of out's shape that receives a widened copy of every element the
+    call writes to out -- from the split-K reduce where the product is split (nsgp_gemm_f32_out64), by a cast launch of the
+    whole of out where it is not."""
     ref = _chk(A, B, out)
     ref, shape, A, M, K, sam, sak, sba, B, N, sbk, sbn, sbb, nb = _gemm_operands(A, B, ta, tb, out)
     if out is None:
         if beta != 0.0:
             raise BackendError('gemm: beta != 0 needs out')
         out = torch.empty(shape, dtype=ref.dtype, device=ref.device)
+    if out64 is not None and (ref.dtype != torch.float32 or out64.dtype != torch.float64 or tuple(out64.shape) != shape
+                              or not out64.is_contiguous() or out64.device != ref.device):
+        raise BackendError(f'gemm: out64 must be a contiguous float64 {shape} beside a float32 product')
     lib = _lib.load()
     wsb = 0 if (flags & GEMM_NO_SPLITK) else lib.nsgp_gemm_workspace(M, N, K, nb, 1, ref.element_size(), int(flags))
     ws = _ws(wsb, ref.device) if wsb else None
     def launch():
-        _lib.call(f'nsgp_gemm_{_sfx(ref)}', M, N, K, float(alpha), _p(A), sam, sak, sba, 0, _p(B), sbk, sbn, sbb, 0,
-                  float(beta), _p(out), N, M * N, 0, nb, 1, int(flags), _p(ws), ws.numel() if ws is not None else 0,
-                  _stream())
+        args = (M, N, K, float(alpha), _p(A), sam, sak, sba, 0, _p(B), sbk, sbn, sbb, 0,
+                float(beta), _p(out), N, M * N, 0, nb, 1, int(flags), _p(ws), ws.numel() if ws is not None else 0,
+                _stream())
+        if out64 is not None:
+            rc = lib.nsgp_gemm_f32_out64(*args, _p(out64), N, M * N, 0)
+            if rc == 0:
+                return
+            if rc != GEMM_OUT64_UNSPLIT:
+                raise BackendError('nsgp_gemm_f32_out64 failed: ' + (f'argument {-rc} invalid' if rc < 0 else f'hipError {rc}'))
+        _lib.call(f'nsgp_gemm_{_sfx(ref)}', *args)
+        if out64 is not None:
+            cast(out, torch.float64, out=out64)
     if _gemm_timer is not None:
         tri = flags & (GEMM_A_LOWER | GEMM_A_UPPER | GEMM_B_LOWER | GEMM_B_UPPER | GEMM_C_LOWER)
         _gemm_timer(launch, 2.0 * M * N * K * nb * (0.5 if tri else 1.0), ref.dtype)

@@ -16,12 +16,66 @@ The backward is 4 more (M x M x n) GEMMs per layer (SVGPLayerFn; the elementwise
 folded into a GEMM epilogue and an operand loader) + one batched M^3 Cholesky adjoint
 (WhitenFn); every identity is checked against torch autograd of the oracle in tests/test_gpu_svgp.py.
 """
+import weakref
+
 import torch
 
 from . import ops
 from .ops import GEMM_A_LOWER, GEMM_A_UPPER, GEMM_B_LOWER, GEMM_B_UPPER, GEMM_C_LOWER, GEMM_C_NOFILL, GEMM_C_HALFDIAG
 
 VAR_JITTER = 1e-4          # data_data_covar.add_jitter(1e-4) in VariationalStrategy.forward
+
+# The whitening adjoint wants the layers' float32 Wbar = tril(Abar Kzx^T) widened into one batched float64 buffer.  The
+# split-K reduce of that product holds every element in a register, so it writes the float64 copy itself (ops.gemm, out64)
+# and WhitenFn.backward's cast launch per layer goes.  The tests switch this off to compare both paths bit for bit.
+_FUSE_WBAR64 = True
+
+
+class _WbarSlots:
+    """The batched float64 Wbar of one whitening chain, shared by WhitenFn.backward and the backward passes of the float32
+    layers that consume its W.  A layer finds the chain through the float64 W it was handed (a view of the chain's batched
+    result: its address names chain and group), writes its group's block and notes which gradient tensor the block
+    mirrors; WhitenFn.backward skips the cast for a group whose incoming gradient is that very tensor, unmodified."""
+    _by_w64 = weakref.WeakValueDictionary()           # address of a group's float64 W -> the chain's slots
+
+    def __init__(self, W64, sizes):
+        self.shape, self.device, self.sizes = tuple(W64.shape), W64.device, list(sizes)
+        self.offs, self.buf, self.sent, off = {}, None, {}, 0
+        for gi, b in enumerate(self.sizes):
+            self.offs[W64[off:off + b].data_ptr()] = gi
+            _WbarSlots._by_w64[W64[off:off + b].data_ptr()] = self
+            off += b
+
+    @staticmethod
+    def find(W64f, W):
+        """(slots, group) for a float32 layer on the float32 W of a chain, with that chain's float64 W64f; else None."""
+        if W64f is None or W64f.dtype != torch.float64 or W.dtype != torch.float32:
+            return None
+        slots = _WbarSlots._by_w64.get(W64f.data_ptr())
+        if slots is None or W64f.data_ptr() not in slots.offs:
+            return None
+        gi = slots.offs[W64f.data_ptr()]
+        ok = tuple(W64f.shape) == (slots.sizes[gi], *slots.shape[1:]) and W64f.is_contiguous() and W64f.device == slots.device
+        return (slots, gi) if ok else None
+
+    def block(self, gi):
+        if self.buf is None:
+            self.buf = torch.empty(self.shape, dtype=torch.float64, device=self.device)
+        off = sum(self.sizes[:gi])
+        return self.buf[off:off + self.sizes[gi]]
+
+    def mirrors(self, gi, g):
+        return self.buf is not None and self.sent.get(gi) == (g.data_ptr(), g._version, tuple(g.shape))
+
+
+def _wbar_product(slot, Abar, Kzx):
+    """Wbar = tril(Abar Kzx^T); with a slot (see _WbarSlots) its float64 copy lands in the whitening chain's buffer."""
+    if slot is None or not _FUSE_WBAR64 or Abar.dtype != torch.float32:
+        return ops.gemm(Abar, Kzx, tb=True, flags=GEMM_C_LOWER)
+    slots, gi = slot
+    Wbar = ops.gemm(Abar, Kzx, tb=True, flags=GEMM_C_LOWER, out64=slots.block(gi))
+    slots.sent[gi] = (Wbar.data_ptr(), Wbar._version, tuple(Wbar.shape))
+    return Wbar
 
 
 class WhitenFn(torch.autograd.Function):
@@ -64,6 +118,8 @@ class WhitenFn(torch.autograd.Function):
         ctx.sizes = [g[0].shape[0] for g in groups]
         ctx.dtypes = [g[0].dtype for g in groups]
         ctx.chol_bwd_f64 = chol_bwd_f64
+        # float32 layers on a float64 chain: their Wbar products fill the adjoint's float64 buffer themselves
+        ctx.wbar_slots = _WbarSlots(W64, ctx.sizes) if (out_dtype == torch.float32 and W64.dtype == torch.float64) else None
         ctx.mark_non_differentiable(info)
         ctx.set_materialize_grads(False)         # no zero-fill launches for outputs nobody differentiated
         # the layers consume W in their own dtype: ONE cast of the batched result here instead of one per layer
@@ -85,11 +141,14 @@ class WhitenFn(torch.autograd.Function):
         if ng == 1 and gouts[0] is not None and gouts[0].dtype == W64.dtype:
             Wbar = gouts[0]
         else:                                    # float64 batched Wbar: cast + placement in one multi-tensor copy
-            Wbar = torch.empty_like(W64)
+            slots = ctx.wbar_slots
+            Wbar = slots.buf if (slots is not None and slots.buf is not None) else torch.empty_like(W64)
             dst, src, off = [], [], 0
             for gi, b in enumerate(ctx.sizes):
                 if gouts[gi] is None:
                     Wbar[off:off + b].zero_()
+                elif slots is not None and slots.mirrors(gi, gouts[gi]):
+                    pass                                 # written by the layer's split-K reduce (_wbar_product)
                 else:
                     dst.append(Wbar[off:off + b])
                     src.append(gouts[gi])
@@ -99,6 +158,8 @@ class WhitenFn(torch.autograd.Function):
                     ops.cast(s_, torch.float64, out=d_)  # matrices took 27 us (few, large tensors), these take 5 + 8
             elif dst:
                 torch._foreach_copy_(dst, src)
+            if slots is not None:
+                slots.sent.clear()
         if ctx.chol_bwd_f64:
             Wb, Wc = Wbar.contiguous(), W64
         else:
@@ -247,6 +308,7 @@ class SVGPLayerFn(torch.autograd.Function):
             Kzx = i8['i8_kzx_out'][0]
         ctx.save_for_backward(x, Z, ls, os_, m, Lq, W, Kzx, A, C, mean_w, mean_c)
         ctx.w_dtype = W64.dtype
+        ctx.wbar_slot = _WbarSlots.find(W64f, W64)
         return mean, var
 
     @staticmethod
@@ -259,7 +321,7 @@ class SVGPLayerFn(torch.autograd.Function):
         Abar, Lqbar, mbar, basebar, wbar, cbar = ops.svgp_project_bwd(Lq, m, A, C, gmean, gvar.contiguous(),
                                                                       affine=affine)
         Kzxbar = ops.gemm(W, Abar, ta=True, flags=GEMM_A_UPPER)                  # W^T Abar
-        Wbar = ops.gemm(Abar, Kzx, tb=True, flags=GEMM_C_LOWER)                  # tril(Abar Kzx^T)
+        Wbar = _wbar_product(ctx.wbar_slot, Abar, Kzx)                           # tril(Abar Kzx^T)
         need_x = ctx.needs_input_grad[0]
         gZ, gx, gls, gos = ops.rbf_build_bwd(Z, x, ls, os_, Kzxbar, need_x1=True, need_x2=need_x)
         gos = gos + basebar
@@ -315,6 +377,7 @@ class SVGPMeanFieldLayerFn(torch.autograd.Function):
             Kzx = kzx_out[0]
         ctx.save_for_backward(x, Z, ls, os_, m, s2m1, W, Kzx, A, mean_w, mean_c)
         ctx.w_dtype = W64.dtype
+        ctx.wbar_slot = _WbarSlots.find(W64f, W64)
         return mean, var
 
     @staticmethod
@@ -326,7 +389,7 @@ class SVGPMeanFieldLayerFn(torch.autograd.Function):
         affine = None if (mean_w is None and mean_c is None) else (x, mean_w, mean_c)
         Abar, mbar, s2bar, basebar, wbar, cbar = ops.svgp_project_diag_bwd(m, s2m1, A, gmean, gvar.contiguous(), affine=affine)
         Kzxbar = ops.gemm(W, Abar, ta=True, flags=GEMM_A_UPPER)                  # W^T Abar
-        Wbar = ops.gemm(Abar, Kzx, tb=True, flags=GEMM_C_LOWER)                  # tril(Abar Kzx^T)
+        Wbar = _wbar_product(ctx.wbar_slot, Abar, Kzx)                           # tril(Abar Kzx^T)
         need_x = ctx.needs_input_grad[0]
         gZ, gx, gls, gos = ops.rbf_build_bwd(Z, x, ls, os_, Kzxbar, need_x1=True, need_x2=need_x)
         gos = gos + basebar
