@@ -419,7 +419,9 @@ int nsgp_svgp_tri_gemm_colstats_i8(const void* Wd, const double* wscale, const v
  *       tri = 2: upper, k >= m; the zeros are in memory), Qt (n x M) bf16 (k contiguous); Y float32 (M x n); YT:
  *       optional bf16 transposed copy of Y (n x M), the Qt operand of the next product; part_dot / part_sq: the
  *       column-statistic partials of nsgp_svgp_tri_gemm_colstats (float32, ceil(M / 128) tile rows = nsgp_svgp_bf16_tiles).
- *   nsgp_cast_sq_bf16_{f32,f64}: dst (b, n, n) bf16 <- src, optionally transposed and / or lower triangle only.
+ *       rowvec may be NULL (then part_dot is not written, and may be NULL too).
+ *   nsgp_cast_sq_bf16_{f32,f64}: dst (b, n, n) bf16 <- src, optionally transposed and / or lower triangle only; nearest-even,
+ *       a float64 source through float32 (the bits of the float32 copy's cast).
  *   nsgp_rbf_build_t_bf16: Kxz[b][i][k] = bf16(os[b] RBF-ARD(x_i, z[b][k]; ls[b])), the transpose of Kzx, k contiguous
  *       (z:(b,M,D) x:(n,D) shared [sxb = 0] or (b,n,D) [sxb = n D]).
  *   nsgp_transpose_cast_bf16: dst (b, n, M) bf16 <- transpose of src (b, M, n) float32 (A -> the Qt operand of product 2

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void bf16_proj_kernel(Bf16Args g, const __b
     __syncthreads();
     if (tid < BN && n0 + tid < g.N) {
         const int64_t o = ((int64_t)bb * g.tiles_m + bm) * g.N + n0 + tid;
-        if (part_dot) part_dot[o] = red[tid] + red[BN + tid];
+        if (part_dot && rv) part_dot[o] = red[tid] + red[BN + tid];    // no rowvec: part_dot is not written
         part_sq[o] = red[2 * BN + tid] + red[3 * BN + tid];
     }
 }
@@ -198,7 +198,11 @@ __global__ void cast_sq_bf16_kernel(const TS* __restrict__ src, __bf16* __restri
     const int64_t i = e / n, j = e % n;                             // destination (i, j)
     const int64_t si = transpose ? j : i, sj = transpose ? i : j;   // source element
     const TS v = (tril && sj > si) ? TS(0) : src[b * n * n + si * n + sj];
-    dst[idx] = (__bf16)(float)v;
+    // float64 -> float32 -> bf16, two roundings, so that a float64 source gives the bits of its float32 copy's cast: left
+    // to itself the compiler folds (__bf16)(float)double into ONE rounding of the double (1 + 2^-8 + 2^-40 -> 0x3F81, not 0x3F80)
+    float f = (float)v;
+    asm volatile("" : "+v"(f));
+    dst[idx] = (__bf16)f;
 }
 
 // Kxz[b][i][k] = bf16( os[b] exp(-1/2 sum_d ((x[i][d] - z[b][k][d]) / ls[b][d])^2) ): the TRANSPOSE of the Kzx the float32

@@ -23,7 +23,7 @@ def _need_gpu():
 
 
 @pytest.mark.parametrize('b,M,n,D,shared_x', [(1, 256, 512, 2, True), (2, 200, 333, 3, True), (3, 128, 64, 3, False),
-                                               (1, 1024, 4096, 2, True)])
+                                               (1, 1024, 4096, 2, True), (1, 136, 129, 2, True), (2, 392, 65, 3, False)])
 def test_bf16_projection_kernels_match_products_of_the_rounded_operands(b, M, n, D, shared_x):
     _need_gpu()
     from nsgp import ops
@@ -63,6 +63,30 @@ def test_bf16_projection_kernels_match_products_of_the_rounded_operands(b, M, n,
     C2_ref = r(torch.tril(Lq)).transpose(-1, -2) @ r(A32.cpu())
     assert float((C2.cpu().double() - C2_ref).abs().max()) < 2e-4 * float(C2_ref.abs().max()) + 1e-5
     assert float((C2 - C32).abs().max()) < 3e-2 * float(C32.abs().max())           # bf16 rounding of both operands
+
+
+def test_bf16_projection_refuses_an_m_that_is_no_multiple_of_8():
+    """The kernels read 16-byte chunks of 8 bf16 along k: the entry point, the planner and the op all refuse M = 20."""
+    _need_gpu()
+    from nsgp import ops
+    from nsgp._lib import BackendError
+    b, M, n, D = 1, 20, 16, 2
+    g = torch.Generator().manual_seed(20)
+    Z, x = torch.randn(b, M, D, generator=g).cuda(), torch.randn(n, D, generator=g).cuda()
+    ls, os_ = torch.ones(b, D).cuda(), torch.ones(b).cuda()
+    W = torch.tril(torch.randn(b, M, M, generator=g)).cuda()
+    Lq, m = torch.eye(M).expand(b, M, M).contiguous().cuda(), torch.randn(b, M, generator=g).cuda()
+    Kzx = ops.rbf_build(Z, x, ls, os_)
+    with pytest.raises(BackendError, match='multiple of 8'):
+        ops.svgp_project_bf16(W, Kzx, Lq, m, os_)
+    with pytest.raises(BackendError, match='multiple of 8'):
+        ops.svgp_project_bf16(W, Kzx, Lq, m, os_, kernel_inputs=(Z, x, ls, os_))
+    for first in ('f32', 'bf16'):
+        with pytest.raises(BackendError, match='M = 20'):
+            ops.svgp_projection_plan(M, n, b, torch.float32, first, 'bf16')
+    with pytest.raises(BackendError, match='M = 20'):
+        ops.svgp_projection_plan(M, n, b, torch.float32, 'bf16', 'diag')
+    assert ops.svgp_projection_plan(24, n, b, torch.float32, 'bf16', 'bf16').second == 'bf16'
 
 
 def test_bf16_forward_at_the_cfg5_shape_states_its_error():
