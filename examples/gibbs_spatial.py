@@ -13,8 +13,11 @@ train-sized `ell1` through gpytorch's joint [train; test] covariance and is shap
 kernel; `predict()` (models/nonstationary_models.py:45-62) is the model's own predictive and is what is used here.)
 `--inference sparse --M 250` runs DiagonalSparseGP with k-means inducing points instead
 (scikit-learn's KMeans; the reference uses pymc3's helper, spatial_exp.py:153).
+`--nu 0.5 | 1.5 | 2.5` (no reference counterpart) swaps the squared-exponential Gibbs kernel for its Matern form,
+GibbsKernel(nu=...): the same lengthscale field, a rougher prior on the precipitation field.
 
     python examples/gibbs_spatial.py --splits 1 --iters 500
+    python examples/gibbs_spatial.py --splits 1 --iters 500 --nu 1.5
 """
 import argparse
 import math
@@ -40,6 +43,8 @@ def main():
     ap.add_argument('--iters', type=int, default=5000)
     ap.add_argument('--inference', choices=('exact', 'sparse'), default='exact')
     ap.add_argument('--M', type=int, default=250)
+    ap.add_argument('--nu', type=float, choices=(0.5, 1.5, 2.5), default=None,
+                    help='non-stationary Matern kernel with this smoothness (default: the Gibbs kernel)')
     ap.add_argument('--prior_scale', type=float, default=1.0)
     ap.add_argument('--prior_ell', type=float, default=1.3)
     ap.add_argument('--prior_mean', type=float, default=0.3)
@@ -80,12 +85,12 @@ def main():
 
         likelihood = gpytorch.likelihoods.GaussianLikelihood().double()
         if args.inference == 'exact':
-            model = DiagonalExactGP(x_train, y_train, likelihood, prior, num_dim=2).to(device).double()
+            model = DiagonalExactGP(x_train, y_train, likelihood, prior, num_dim=2, nu=args.nu).to(device).double()
         else:
             from sklearn.cluster import KMeans
             z = torch.tensor(KMeans(args.M, n_init=1, random_state=BASE_SEED + i).fit(x_train.cpu().numpy())
                              .cluster_centers_).double()
-            model = DiagonalSparseGP(x_train, y_train, likelihood, prior, z, num_dim=2).to(device).double()
+            model = DiagonalSparseGP(x_train, y_train, likelihood, prior, z, num_dim=2, nu=args.nu).to(device).double()
         if args.noise > 0:
             model.likelihood.noise = args.noise
             for p in model.likelihood.noise_covar.parameters():

@@ -81,6 +81,34 @@ int nsgp_gibbs_build_bwd_f64(const double* x1, const double* x2, const double* e
                              void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K1' Non-stationary Matern kernel (Paciorek & Schervish 2006 with Sigma(x) = diag ell(x)^2): K1 with the stationary
+ *     Matern radial function in place of the squared exponential,
+ *     K[i,j] = os * prod_d sqrt(2 l1[d,i] l2[d,j] / s_d) * k_nu(sqrt(s)),  s_d = l1[d,i]^2 + l2[d,j]^2,
+ *              s = 2 sum_d (x1[i,d]-x2[j,d])^2 / s_d   (+ diag_add on i==j),   k_nu as K2'' below.
+ *     (K1 is the same expression with e^{-s/2} for k_nu; ell1 = ell2 = const gives os * Matern-ARD(ell).)
+ *     The K1 signatures with nu2 = 2 nu in {1, 3, 5} after D (any other value: argument 8 invalid); layouts, NULL
+ *     scalars, the outputs of the backward and its summing mode are K1's, and the backward takes its workspace size from
+ *     nsgp_gibbs_build_bwd_workspace.  For nu = 1/2 the derivative at zero distance is taken as 0, as in K2''.
+ *     An empty problem (n1 or n2 = 0) returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------ */
+int nsgp_gibbs_matern_build_fwd_f32(const float* x1, const float* x2, const float* ell1, const float* ell2,
+                                    int64_t n1, int64_t n2, int D, int nu2, const float* outputscale,
+                                    const float* diag_add, float* K, int64_t ldk, void* stream);
+int nsgp_gibbs_matern_build_fwd_f64(const double* x1, const double* x2, const double* ell1, const double* ell2,
+                                    int64_t n1, int64_t n2, int D, int nu2, const double* outputscale,
+                                    const double* diag_add, double* K, int64_t ldk, void* stream);
+int nsgp_gibbs_matern_build_bwd_f32(const float* x1, const float* x2, const float* ell1, const float* ell2,
+                                    int64_t n1, int64_t n2, int D, int nu2, const float* outputscale,
+                                    const float* G, int64_t ldg,
+                                    float* g_ell1, float* g_ell2, float* g_x1, float* g_x2, float* g_os,
+                                    void* ws, size_t ws_bytes, void* stream);
+int nsgp_gibbs_matern_build_bwd_f64(const double* x1, const double* x2, const double* ell1, const double* ell2,
+                                    int64_t n1, int64_t n2, int D, int nu2, const double* outputscale,
+                                    const double* G, int64_t ldg,
+                                    double* g_ell1, double* g_ell2, double* g_x1, double* g_x2, double* g_os,
+                                    void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K2  Batched RBF-ARD kernel  K[b,i,j] = os[b] * exp(-0.5 sum_d ((x1[b,i,d]-x2[b,j,d])/ls[b,d])^2)
  *     replaces gpytorch ScaleKernel(RBFKernel(ard)) as built at models/dgps.py:44-46 and
  *     models/gibbs_kernels.py:67-69.  x1:(batch,n1,D) with batch stride sx1 (0 = shared),

@@ -1,6 +1,6 @@
 // pairwise.hip -- kernel-matrix builds K[i,j] = k(row_i, col_j) and their backward reductions.
 //
-//   K1 Gibbs (models/gibbs_kernels.py:154-162), K2 batched RBF-ARD (gpytorch ScaleKernel(RBF),
+//   K1 Gibbs (models/gibbs_kernels.py:154-162), K1' its Matern form (GibbsRadialOp), K2 batched RBF-ARD (gpytorch ScaleKernel(RBF),
 //   models/dgps.py:44-46), K3 Paciorek-Schervish D=2 (models/multivariate_gibbs_kernel.py:98-150).
 //
 // Layout: a functor per kernel family (GibbsOp, ArdOp, RbfPeriodicOp, PsOp) is plugged into ONE forward tile kernel and
@@ -239,6 +239,86 @@ template <typename T, int D, typename Radial> struct ArdOp {
                 ra[d] += w * df;
                 ca[d] -= w * df;
                 ga[d] -= w * df * df;
+            }
+        }
+    }
+};
+
+// K1' non-stationary Matern (Paciorek & Schervish 2006 with Sigma(x) = diag l(x)^2):  k = os * P * kappa(s), the Gibbs
+// prefactor P = prod_d sqrt(2 l1 l2 / s_d) = h1 h2 rsqrt(S) times the stationary radial function at the squared distance
+// s = 2 sum_d delta_d^2 / s_d = 2 num / S (GibbsOp::base's variables; kappa = e^{-s/2} is GibbsOp itself).  A sibling of
+// GibbsOp, not a respelling of it: the per-point operands (P, point, row, col, fcol) and the accumulator layout are
+// inherited, so the launchers, the OutDesc wiring, the workspace size and the symmetric mode are GibbsOp's, and GibbsOp's
+// own code -- whose float32 bits depend on its spelling under -ffp-contract=fast -- is not touched.
+// Per entry: one rsqrt, one distance (matern_dist) and one exp (matern_poly_exp).
+// With phi = (d kappa / d d) / d as the policy returns it, q_d = delta_d^2 / s_d^2 and a = l1_d (b = l2_d alike):
+//   dk/da    = os P [kappa (1/(2a) - a / s_d) - 2 phi a q_d]
+//   dk/dx1_d = 2 os P phi delta_d / s_d = -dk/dx2_d            dk/dos = P kappa
+template <typename T, int D, typename Radial> struct GibbsRadialOp : GibbsOp<T, D> {
+    using G = GibbsOp<T, D>;
+    using P = typename G::P;
+    static constexpr int DM = G::DM;
+    // the prefactor h1 h2 rsqrt(S) (returned) and the squared distance s.  BWD: s_d from l, not from the stored q -- the
+    // backward keeps four column operands per lane, and with q live as well the generic float64 instance spilled
+    // (364 B of scratch per lane; the per-dimension reciprocals of grad below were the rest)
+    static __device__ __forceinline__ T lsq(T a, T b) { return t_fma(a, a, b * b); }      // s_d, one spelling
+    template <bool BWD = false> __device__ __forceinline__ T pre(const P& r, const P& c, T& s) const {
+        T S = BWD ? lsq(r.l[0], c.l[0]) : r.q[0] + c.q[0];
+        T num = (r.x[0] - c.x[0]) * (r.x[0] - c.x[0]);
+#pragma unroll
+        for (int d = 1; d < DM; ++d) {
+            if (D || d < this->Drt) {
+                const T sd = BWD ? lsq(r.l[d], c.l[d]) : r.q[d] + c.q[d];
+                const T df = r.x[d] - c.x[d];
+                // explicit: left to -ffp-contract the compiler fused this sum for two of a lane's four float32 columns
+                // and not for the other two (nu = 5/2, D = 2), and K(x, x) was symmetric to several ulp only
+                num = t_fma(df * df, S, num * sd);
+                S *= sd;
+            }
+        }
+        const T rs = t_rsqrt(S);
+        s = T(2) * num * rs * rs;
+        return r.h * c.h * rs;
+    }
+    __device__ __forceinline__ T base(const P& r, const P& c) const {
+        T s;
+        const T p = pre(r, c, s);
+        return p * Radial::eval(s);
+    }
+    __device__ __forceinline__ T eval(int64_t, const P& r, const P& c) const { return this->os() * base(r, c); }
+    __device__ __forceinline__ T feval(int64_t, const P& r, const P& c) const { return base(r, c); }
+    __device__ __forceinline__ void grad(int64_t, const P& r, const P& c, T g, T* ra, T* ca, T* ga) const {
+        T s, q;
+        const T p = this->template pre<true>(r, c, s);
+        const T kap = Radial::eval(s, &q);
+        ga[0] += g * (p * kap);
+        const T w = g * p * this->os();
+        const T wk = w * kap, wq = w * q;             // wq = w phi, or -w phi for a negated policy
+#pragma unroll
+        for (int d = 0; d < DM; ++d) {
+            if (D || d < this->Drt) {
+                // one division per dimension: u = 1 / (2 a b s_d) gives 1 / s_d = 2 a b u, and
+                // 1/(2a) - a / s_d = -b t,  1/(2b) - b / s_d = a t  with  t = (a - b)(a + b) u
+                const T a = r.l[d], b = c.l[d];
+                const T sd = lsq(a, b);
+                const T ab2 = T(2) * a * b;
+                const T u = T(1) / (ab2 * sd);
+                const T inv = ab2 * u;
+                const T t = wk * ((a - b) * (a + b) * u);
+                const T df = r.x[d] - c.x[d];
+                const T gx = T(2) * wq * df * inv;                   // 2 w (+-phi) delta / s_d
+                const T qd = gx * df * inv;                          // 2 w (+-phi) delta^2 / s_d^2
+                if constexpr (Radial::negated) {
+                    ra[d] += a * qd - b * t;
+                    ca[d] += b * qd + a * t;
+                    ra[DM + d] -= gx;
+                    ca[DM + d] += gx;
+                } else {
+                    ra[d] -= a * qd + b * t;
+                    ca[d] += a * t - b * qd;
+                    ra[DM + d] += gx;
+                    ca[DM + d] -= gx;
+                }
             }
         }
     }
@@ -682,6 +762,24 @@ int gibbs_fwd(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, in
     });
 }
 
+// The backward launch of the Gibbs family (GibbsOp, GibbsRadialOp): one accumulator layout, so one output wiring.
+template <typename T, typename Op>
+int gibbs_launch_bwd(const Op& op, const T* G, int64_t ldg, T* g_l1, T* g_l2, T* g_x1, T* g_x2, T* g_os, void* ws,
+                     size_t wsb, void* stream) {
+    constexpr int DM = Op::DM;
+    const int D = op.Drt;
+    const int64_t n1 = op.n1, n2 = op.n2;
+    OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
+    for (int d = 0; d < D; ++d) {
+        if (g_l1) { rows.ptr[d] = g_l1 + (int64_t)d * n1; rows.stride[d] = 1; }
+        if (g_x1) { rows.ptr[DM + d] = g_x1 + d; rows.stride[DM + d] = D; }
+        if (g_l2) { cols.ptr[d] = g_l2 + (int64_t)d * n2; cols.stride[d] = 1; }
+        if (g_x2) { cols.ptr[DM + d] = g_x2 + d; cols.stride[DM + d] = D; }
+    }
+    globs.ptr[0] = g_os;
+    return launch_bwd<T>(op, 1, n1, n2, G, ldg, 0, rows, cols, globs, ws, wsb, stream);
+}
+
 template <typename T>
 int gibbs_bwd(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, int64_t n2, int D, const T* os, const T* G,
               int64_t ldg, T* g_l1, T* g_l2, T* g_x1, T* g_x2, T* g_os, void* ws, size_t wsb, void* stream) {
@@ -689,18 +787,8 @@ int gibbs_bwd(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, in
     if (n1 < 0) return -5; if (n2 < 0) return -6; if (D < 1 || D > NSGP_MAX_DIM) return -7;
     if (!G && n1 * n2 > 0) return -9; if (ldg < n2) return -10;
     return dispatch_dim<1, 2, 3>(D, [&](auto dim) {
-        using Op = GibbsOp<T, decltype(dim)::value>;
-        Op op{x1, x2, l1, l2, n1, n2, D, os};
-        constexpr int DM = Op::DM;
-        OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
-        for (int d = 0; d < D; ++d) {
-            if (g_l1) { rows.ptr[d] = g_l1 + (int64_t)d * n1; rows.stride[d] = 1; }
-            if (g_x1) { rows.ptr[DM + d] = g_x1 + d; rows.stride[DM + d] = D; }
-            if (g_l2) { cols.ptr[d] = g_l2 + (int64_t)d * n2; cols.stride[d] = 1; }
-            if (g_x2) { cols.ptr[DM + d] = g_x2 + d; cols.stride[DM + d] = D; }
-        }
-        globs.ptr[0] = g_os;
-        return launch_bwd<T>(op, 1, n1, n2, G, ldg, 0, rows, cols, globs, ws, wsb, stream);
+        GibbsOp<T, decltype(dim)::value> op{x1, x2, l1, l2, n1, n2, D, os};
+        return gibbs_launch_bwd<T>(op, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb, stream);
     });
 }
 
@@ -798,6 +886,38 @@ int matern_bwd(const T* x1, const T* x2, const T* ls, const T* os, int64_t batch
     if (const int bad = ard_check(a, 1, matern_nu2_ok(nu2), G, ldg, ARD_BWD_G)) return bad;
     return dispatch_nu2(nu2, [&](auto radial) {
         return ard_bwd<T, decltype(radial)>(a, G, ldg, sG, g_x1, g_x2, g_ls, g_os, ws, wsb, stream);
+    });
+}
+
+// K1': the Gibbs signatures with nu2 after D (so every later argument's index is one up)
+template <typename T>
+int gibbs_matern_fwd(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, int64_t n2, int D, int nu2,
+                     const T* os, const T* diag_add, T* K, int64_t ldk, void* stream) {
+    if (!x1) return -1; if (!x2) return -2; if (!l1) return -3; if (!l2) return -4;
+    if (n1 < 0) return -5; if (n2 < 0) return -6; if (D < 1 || D > NSGP_MAX_DIM) return -7;
+    if (!matern_nu2_ok(nu2)) return -8;
+    if (!K && n1 * n2 > 0) return -11; if (ldk < n2) return -12;
+    return dispatch_nu2(nu2, [&](auto radial) {
+        return dispatch_dim<1, 2, 3>(D, [&](auto d) {
+            GibbsRadialOp<T, decltype(d)::value, decltype(radial)> op{{x1, x2, l1, l2, n1, n2, D, os}};
+            return launch_fwd<T>(op, 1, n1, n2, T(0), diag_add, K, ldk, 0, stream);
+        });
+    });
+}
+
+template <typename T>
+int gibbs_matern_bwd(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, int64_t n2, int D, int nu2,
+                     const T* os, const T* G, int64_t ldg, T* g_l1, T* g_l2, T* g_x1, T* g_x2, T* g_os, void* ws,
+                     size_t wsb, void* stream) {
+    if (!x1) return -1; if (!x2) return -2; if (!l1) return -3; if (!l2) return -4;
+    if (n1 < 0) return -5; if (n2 < 0) return -6; if (D < 1 || D > NSGP_MAX_DIM) return -7;
+    if (!matern_nu2_ok(nu2)) return -8;
+    if (!G && n1 * n2 > 0) return -10; if (ldg < n2) return -11;
+    return dispatch_nu2(nu2, [&](auto radial) {
+        return dispatch_dim<1, 2, 3>(D, [&](auto dim) {
+            GibbsRadialOp<T, decltype(dim)::value, decltype(radial)> op{{x1, x2, l1, l2, n1, n2, D, os}};
+            return gibbs_launch_bwd<T>(op, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb, stream);
+        });
     });
 }
 
@@ -899,6 +1019,31 @@ int nsgp_gibbs_build_bwd_f64(const double* x1, const double* x2, const double* l
                              double* g_l2, double* g_x1, double* g_x2, double* g_os, void* ws, size_t wsb,
                              void* stream) {
     return gibbs_bwd<double>(x1, x2, l1, l2, n1, n2, D, os, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb, stream);
+}
+
+int nsgp_gibbs_matern_build_fwd_f32(const float* x1, const float* x2, const float* l1, const float* l2, int64_t n1,
+                                    int64_t n2, int D, int nu2, const float* os, const float* diag_add, float* K,
+                                    int64_t ldk, void* stream) {
+    return gibbs_matern_fwd<float>(x1, x2, l1, l2, n1, n2, D, nu2, os, diag_add, K, ldk, stream);
+}
+int nsgp_gibbs_matern_build_fwd_f64(const double* x1, const double* x2, const double* l1, const double* l2, int64_t n1,
+                                    int64_t n2, int D, int nu2, const double* os, const double* diag_add, double* K,
+                                    int64_t ldk, void* stream) {
+    return gibbs_matern_fwd<double>(x1, x2, l1, l2, n1, n2, D, nu2, os, diag_add, K, ldk, stream);
+}
+int nsgp_gibbs_matern_build_bwd_f32(const float* x1, const float* x2, const float* l1, const float* l2, int64_t n1,
+                                    int64_t n2, int D, int nu2, const float* os, const float* G, int64_t ldg,
+                                    float* g_l1, float* g_l2, float* g_x1, float* g_x2, float* g_os, void* ws,
+                                    size_t wsb, void* stream) {
+    return gibbs_matern_bwd<float>(x1, x2, l1, l2, n1, n2, D, nu2, os, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb,
+                                   stream);
+}
+int nsgp_gibbs_matern_build_bwd_f64(const double* x1, const double* x2, const double* l1, const double* l2, int64_t n1,
+                                    int64_t n2, int D, int nu2, const double* os, const double* G, int64_t ldg,
+                                    double* g_l1, double* g_l2, double* g_x1, double* g_x2, double* g_os, void* ws,
+                                    size_t wsb, void* stream) {
+    return gibbs_matern_bwd<double>(x1, x2, l1, l2, n1, n2, D, nu2, os, G, ldg, g_l1, g_l2, g_x1, g_x2, g_os, ws, wsb,
+                                    stream);
 }
 
 int nsgp_rbf_build_fwd_f32(const float* x1, const float* x2, const float* ls, const float* os, int64_t batch,

@@ -3,7 +3,7 @@ models/gibbs_kernels.py of the reference (same names, argument meaning and error
 
   PositivePriorProcess                       reference models/gibbs_kernels.py:35-59
   LogNormalPriorProcess(input_dim=1, covariance_function=None, active_dims=None)      :61-109
-  GibbsKernel(*a, lengthscale_prior=None, **kw).forward(x1, x2, ell1=None, ell2=None) :111-162
+  GibbsKernel(*a, lengthscale_prior=None, nu=None, **kw).forward(x1, x2, ell1=None, ell2=None) :111-162
   GibbsSafeScaleKernel                                                                 :164-168
   InducingGibbsKernel(base_kernel, inducing_points, likelihood, active_dims=None)      :171-266
   InducingGibbsKernelST (same, slicing inducing points by active_dims)                 :268-363
@@ -90,15 +90,21 @@ class LogNormalPriorProcess(PositivePriorProcess):
 
 
 class GibbsKernel(gpytorch.kernels.Kernel):
-    """Diagonal Gibbs kernel (Rasmussen & Williams eq. 4.32) with a prior process on ell(x)."""
+    """Diagonal Gibbs kernel (Rasmussen & Williams eq. 4.32) with a prior process on ell(x).
+    nu = None is that squared-exponential kernel; nu in {0.5, 1.5, 2.5} is the non-stationary Matern kernel of Paciorek &
+    Schervish (2006) with the same prefactor, k = os * prod_d sqrt(2 l1 l2 / s_d) * Matern_nu(sqrt(2 sum_d delta_d^2 / s_d)),
+    s_d = l1_d^2 + l2_d^2: ell(x) still says where the field varies fast, nu how rough it is."""
 
     is_stationary = False
     fuses_outputscale = True           # GibbsSafeScaleKernel folds its outputscale into the same launch
     fuses_diag_add = True              # ... and likelihood(dist) folds noise * I into it too
 
-    def __init__(self, *args, lengthscale_prior: PositivePriorProcess = None, **kwargs) -> None:
+    def __init__(self, *args, lengthscale_prior: PositivePriorProcess = None, nu=None, **kwargs) -> None:
+        if nu is not None and nu not in {0.5, 1.5, 2.5}:
+            raise RuntimeError('nu expected to be 0.5, 1.5, or 2.5')
         super().__init__(*args, **kwargs)
         self.lengthscale_prior = lengthscale_prior
+        self.nu = nu
 
     @property
     def batch_shape(self):
@@ -117,7 +123,7 @@ class GibbsKernel(gpytorch.kernels.Kernel):
         elif ell2 is None:
             ell2 = self.lengthscale_prior.conditional_sample(x2, given=(x1, ell1))
             self.ell2 = ell2
-        return ops.gibbs_kernel(x1, x2, ell1, ell2, _outputscale, _diag_add)
+        return ops.gibbs_kernel(x1, x2, ell1, ell2, _outputscale, _diag_add, nu=self.nu)
 
 
 class GibbsSafeScaleKernel(gpytorch.kernels.ScaleKernel):

@@ -1,8 +1,10 @@
 """MAP exact GP and SGPR GP over the Gibbs kernel on the MI355X engine -- drop-in for
 models/nonstationary_models.py of the reference.
 
-  DiagonalExactGP(train_x, train_y, likelihood, prior, num_dim=1)      reference :22-62
-  DiagonalSparseGP(train_x, train_y, likelihood, prior, z, num_dim=1)  reference :64-153
+  DiagonalExactGP(train_x, train_y, likelihood, prior, num_dim=1, *, nu=None)      reference :22-62
+  DiagonalSparseGP(train_x, train_y, likelihood, prior, z, num_dim=1, *, nu=None)  reference :64-153
+nu (no reference counterpart) is handed to GibbsKernel: None is the reference's squared-exponential Gibbs kernel, 0.5,
+1.5 or 2.5 its Matern form.
 Both behave like an ExactGP in training (forward on the training inputs, trained with
 ExactMarginalLogLikelihood); predictions are made with .predict(x_new), which returns an MVN with
 .loc / .covariance_matrix / .log_prob like the reference.  The reference's explicit torch.inverse
@@ -22,10 +24,10 @@ class DiagonalExactGP(gpytorch.models.ExactGP):
     """MAP inference of a diagonal-Gibbs-kernel GP: log ell at the training points is a parameter
     (D, N), initialised at the prior mean and regularised by the prior process."""
 
-    def __init__(self, train_x, train_y, likelihood, prior, num_dim=1):
+    def __init__(self, train_x, train_y, likelihood, prior, num_dim=1, *, nu=None):
         super().__init__(train_x, train_y, likelihood)
         self.mean_module = gpytorch.means.ZeroMean()
-        self.covar_module = GibbsSafeScaleKernel(GibbsKernel(lengthscale_prior=prior, ard_num_dims=num_dim))
+        self.covar_module = GibbsSafeScaleKernel(GibbsKernel(lengthscale_prior=prior, ard_num_dims=num_dim, nu=nu))
         self.register_parameter('log_ell_train_x', torch.nn.Parameter(prior.mean_module(train_x).detach().clone()))
         self.register_prior('ell_train_prior', prior, lambda module: (module.train_inputs[0], module.log_ell_train_x))
 
@@ -55,11 +57,11 @@ class DiagonalExactGP(gpytorch.models.ExactGP):
 class DiagonalSparseGP(gpytorch.models.ExactGP):
     """MAP inference of the sparse (SGPR) Gibbs-kernel GP: log ell lives at the inducing points."""
 
-    def __init__(self, train_x, train_y, likelihood, prior, z, num_dim=1):
+    def __init__(self, train_x, train_y, likelihood, prior, z, num_dim=1, *, nu=None):
         super().__init__(train_x, train_y, likelihood)
         self.mean_module = gpytorch.means.ZeroMean()
         self.covar_module = GibbsSafeScaleKernel(
-            InducingGibbsKernel(GibbsKernel(lengthscale_prior=prior, ard_num_dims=num_dim), z, likelihood))
+            InducingGibbsKernel(GibbsKernel(lengthscale_prior=prior, ard_num_dims=num_dim, nu=nu), z, likelihood))
         self.register_parameter('log_ell_z', torch.nn.Parameter(prior.mean_module(z).detach().clone()))
         self.register_prior('ell_z_prior', prior,
                             lambda module: (module.covar_module.base_kernel.inducing_points, module.log_ell_z))

@@ -39,13 +39,14 @@ class SpatioTemporal_Stationary(gpytorch.models.ExactGP):
 
 class SparseSpatioTemporal_Nonstationary(gpytorch.models.ExactGP):
     """MAP inference of the sparse Gibbs-kernel GP over (lon, lat) plus an SGPR temporal component that shares
-    the spatial kernel's inducing points (frozen for the temporal part, spatio_temporal_models.py:42-43)."""
+    the spatial kernel's inducing points (frozen for the temporal part, spatio_temporal_models.py:42-43).
+    nu (keyword-only): None is the Gibbs kernel, 0.5, 1.5 or 2.5 its Matern form (GibbsKernel)."""
 
-    def __init__(self, train_x, train_y, likelihood, prior, z, num_dim=1):
+    def __init__(self, train_x, train_y, likelihood, prior, z, num_dim=1, *, nu=None):
         super().__init__(train_x, train_y, likelihood)
         self.mean_module = gpytorch.means.ZeroMean()
         self.spatial_covar_module = GibbsSafeScaleKernel(
-            InducingGibbsKernelST(GibbsKernel(lengthscale_prior=prior, active_dims=(0, 1)), inducing_points=z,
+            InducingGibbsKernelST(GibbsKernel(lengthscale_prior=prior, active_dims=(0, 1), nu=nu), inducing_points=z,
                                   likelihood=likelihood, active_dims=(1, 2)), active_dims=(1, 2))
         self.temporal_covar_module = InducingPointKernel(
             _temporal_kernel(), inducing_points=self.spatial_covar_module.base_kernel.inducing_points,

@@ -159,8 +159,11 @@ def _scalar_dev(v, like):
 
 
 # --------------------------------------------------------------------------------------------
-# K1 Gibbs
+# K1 Gibbs, K1' its Matern form
 # --------------------------------------------------------------------------------------------
+MATERN_NU = (0.5, 1.5, 2.5)
+
+
 def _gibbs_args(x1, x2, ell1, ell2):
     ref = _chk(x1, x2, ell1, ell2)
     if x1.dim() != 2 or x2.dim() != 2 or ell1.dim() != 2 or ell2.dim() != 2:
@@ -183,19 +186,33 @@ def _out_matrix(out, shape, ref):
     return out
 
 
-def gibbs_build(x1, x2, ell1, ell2, outputscale=None, diag_add=None, out=None):
-    """K = os * Gibbs(x1,x2; ell1,ell2) (+ diag_add on the diagonal).  models/gibbs_kernels.py:154-162."""
+def _gibbs_entry(nu):
+    """(library stem, the scalars its entry points take after D) of the Gibbs build: nu = None is the squared-exponential
+    kernel, nu in {0.5, 1.5, 2.5} its Matern form (K1', nu2 = 2 nu).  Any other value raises as gpytorch's MaternKernel."""
+    if nu is None:
+        return 'gibbs', ()
+    if nu not in MATERN_NU:
+        raise RuntimeError('nu expected to be 0.5, 1.5, or 2.5')
+    return 'gibbs_matern', (int(2 * nu),)
+
+
+def gibbs_build(x1, x2, ell1, ell2, outputscale=None, diag_add=None, out=None, nu=None):
+    """K = os * Gibbs(x1,x2; ell1,ell2) (+ diag_add on the diagonal).  models/gibbs_kernels.py:154-162.
+    nu in {0.5, 1.5, 2.5}: the non-stationary Matern kernel os * P * Matern_nu(sqrt(2 sum_d delta_d^2 / s_d)) with the
+    same prefactor P (include/nsgp.h, K1')."""
+    stem, extra = _gibbs_entry(nu)
     ref, n1, n2, D = _gibbs_args(x1, x2, ell1, ell2)
     x1, x2, ell1, ell2 = _c(x1), _c(x2), _c(ell1), _c(ell2)
     os_ = None if outputscale is None else _scalar_dev(outputscale, ref)
     da = None if diag_add is None else _scalar_dev(diag_add, ref)
     K = _out_matrix(out, (n1, n2), ref)
-    _lib.call(f'nsgp_gibbs_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ell1), _p(ell2), n1, n2, D,
+    _lib.call(f'nsgp_{stem}_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ell1), _p(ell2), n1, n2, D, *extra,
               _p(os_), _p(da), _p(K), n2, _stream())
     return K
 
 
-def gibbs_build_bwd(x1, x2, ell1, ell2, outputscale, G, need_x=False, need_os=True):
+def gibbs_build_bwd(x1, x2, ell1, ell2, outputscale, G, need_x=False, need_os=True, nu=None):
+    stem, extra = _gibbs_entry(nu)
     ref, n1, n2, D = _gibbs_args(x1, x2, ell1, ell2)
     _chk(ref, G)
     if G.shape != (n1, n2):
@@ -209,7 +226,7 @@ def gibbs_build_bwd(x1, x2, ell1, ell2, outputscale, G, need_x=False, need_os=Tr
     lib = _lib.load()
     wsb = lib.nsgp_gibbs_build_bwd_workspace(n1, n2, D, ref.element_size())
     ws = _ws(wsb, ref.device)
-    _lib.call(f'nsgp_gibbs_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ell1), _p(ell2), n1, n2, D, _p(os_),
+    _lib.call(f'nsgp_{stem}_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ell1), _p(ell2), n1, n2, D, *extra, _p(os_),
               _p(G), n2, _p(g_l1), _p(g_l2), _p(g_x1), _p(g_x2), _p(g_os), _p(ws), ws.numel(), _stream())
     return g_l1, g_l2, g_x1, g_x2, g_os
 
@@ -288,9 +305,6 @@ def rbf_build_bwd(x1, x2, ls, os_, G, need_x1=True, need_x2=True, sym=False):
 # --------------------------------------------------------------------------------------------
 # K2'' Matern-ARD (batched), nu in {1/2, 3/2, 5/2}
 # --------------------------------------------------------------------------------------------
-MATERN_NU = (0.5, 1.5, 2.5)
-
-
 def _nu2(nu):
     if nu not in MATERN_NU:
         raise BackendError(f'matern_build: nu must be one of {MATERN_NU}, got {nu}')
@@ -1301,20 +1315,21 @@ def adam_step_(p, g, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scal
 class GibbsKernelFn(torch.autograd.Function):
     """K = os * Gibbs(x1,x2;ell1,ell2) + diag_add*I  (GibbsKernel.forward under GibbsSafeScaleKernel,
     models/gibbs_kernels.py:135-168).  Pass the same tensor as ell1 and ell2 for K_xx: autograd then
-    sums both roles."""
+    sums both roles.  nu = None: the squared-exponential kernel; 0.5, 1.5, 2.5: its Matern form."""
 
     @staticmethod
-    def forward(ctx, x1, x2, ell1, ell2, outputscale, diag_add):
+    def forward(ctx, x1, x2, ell1, ell2, outputscale, diag_add, nu=None):
         ctx.save_for_backward(x1, x2, ell1, ell2, outputscale)
+        ctx.nu = nu
         ctx.has_diag = diag_add is not None
         ctx.diag_shape = diag_add.shape if torch.is_tensor(diag_add) else None
-        return gibbs_build(x1, x2, ell1, ell2, outputscale, diag_add)
+        return gibbs_build(x1, x2, ell1, ell2, outputscale, diag_add, nu=nu)
 
     @staticmethod
     def backward(ctx, G):
         x1, x2, ell1, ell2, outputscale = ctx.saved_tensors
         need_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        g_l1, g_l2, g_x1, g_x2, g_os = gibbs_build_bwd(x1, x2, ell1, ell2, outputscale, G, need_x=need_x)
+        g_l1, g_l2, g_x1, g_x2, g_os = gibbs_build_bwd(x1, x2, ell1, ell2, outputscale, G, need_x=need_x, nu=ctx.nu)
         g_diag = None
         if ctx.has_diag and ctx.needs_input_grad[5]:
             g_diag = torch.diagonal(G).sum().reshape(ctx.diag_shape if ctx.diag_shape is not None else ())
@@ -1323,7 +1338,7 @@ class GibbsKernelFn(torch.autograd.Function):
             g_osr = g_os.reshape(outputscale.shape)
         return (g_x1 if ctx.needs_input_grad[0] else None, g_x2 if ctx.needs_input_grad[1] else None,
                 g_l1 if ctx.needs_input_grad[2] else None, g_l2 if ctx.needs_input_grad[3] else None,
-                g_osr, g_diag)
+                g_osr, g_diag, None)
 
 
 def _sum_shared(g_x, x, needed):
@@ -1484,8 +1499,8 @@ def chol_inv(K):
     return CholInvFn.apply(K)
 
 
-def gibbs_kernel(x1, x2, ell1, ell2, outputscale=None, diag_add=None):
-    return GibbsKernelFn.apply(x1, x2, ell1, ell2, outputscale, diag_add)
+def gibbs_kernel(x1, x2, ell1, ell2, outputscale=None, diag_add=None, nu=None):
+    return GibbsKernelFn.apply(x1, x2, ell1, ell2, outputscale, diag_add, nu)
 
 
 def rbf_kernel(x1, x2, ls, os_, diag_add=0.0):

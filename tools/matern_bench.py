@@ -1,11 +1,11 @@
 """Event-timed pairwise builds at N = 4096 and 16384, D = 2, batch 1: one JSON line per case.
 
-    python tools/matern_bench.py [--tree PATH] [--kernels matern gibbs rbf] [--n 4096 16384] [--dtype f32 f64]
+    python tools/matern_bench.py [--tree PATH] [--kernels matern gibbs gibbs_matern rbf] [--n 4096 16384] [--dtype f32 f64]
 
-Cases: `matern` (nu = 1/2, 3/2, 5/2), `gibbs` (ops.gibbs_build with an outputscale) and `rbf`, each as the forward
-build alone (`fwd`) and as forward + backward (`fwdbwd`, the backward of K(x, x) with every gradient).  --tree imports
-nsgp from another checkout of this repository (e.g. the parent commit's, for a baseline: it has no Matern kernel, so
-run it with --kernels gibbs rbf).
+Cases: `matern` (nu = 1/2, 3/2, 5/2), `gibbs` (ops.gibbs_build with an outputscale), `gibbs_matern` (the same call with
+nu = 1/2, 3/2, 5/2: the non-stationary Matern kernel) and `rbf`, each as the forward build alone (`fwd`) and as forward +
+backward (`fwdbwd`, the backward of K(x, x) with every gradient).  --tree imports nsgp from another checkout of this
+repository (e.g. a parent commit's, for a baseline; name only the kernels that checkout has).
 
 Each case: `--warmup` untimed launches, then `--reps` timed launches, each between its own pair of events; the line
 reports the median ms.  TB/s uses the algorithmic bytes of csrc/pairwise.hip's header, s (n1 n2 + 2 D (n1 + n2)) for
@@ -24,7 +24,8 @@ import torch
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--tree', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    ap.add_argument('--kernels', nargs='+', default=['matern', 'gibbs', 'rbf'], choices=['matern', 'gibbs', 'rbf'])
+    ap.add_argument('--kernels', nargs='+', default=['matern', 'gibbs', 'gibbs_matern', 'rbf'],
+                    choices=['matern', 'gibbs', 'gibbs_matern', 'rbf'])
     ap.add_argument('--n', nargs='+', type=int, default=[4096, 16384])
     ap.add_argument('--dtype', nargs='+', default=['f32', 'f64'], choices=['f32', 'f64'])
     ap.add_argument('--passes', nargs='+', default=['fwd', 'fwdbwd'], choices=['fwd', 'fwdbwd'])
@@ -57,6 +58,11 @@ def main():
                 elif k == 'gibbs':
                     cases.append(('gibbs', lambda: ops.gibbs_build(x, x, ell, ell, outputscale=os_, out=K[0]),
                                   lambda: ops.gibbs_build_bwd(x, x, ell, ell, os_, G, need_x=True)))
+                elif k == 'gibbs_matern':
+                    for nu in (0.5, 1.5, 2.5):
+                        cases.append((f'gibbs_matern{nu}',
+                                      lambda nu=nu: ops.gibbs_build(x, x, ell, ell, outputscale=os_, out=K[0], nu=nu),
+                                      lambda nu=nu: ops.gibbs_build_bwd(x, x, ell, ell, os_, G, need_x=True, nu=nu)))
                 else:
                     cases.append(('rbf', lambda: ops.rbf_build(x, x, ls, os_, out=K),
                                   lambda: ops.rbf_build_bwd(x, x, ls, os_, G)))
