@@ -9,6 +9,7 @@ covariances (SGPR training) through the M x M Woodbury system."""
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import ops
 from . import settings
@@ -38,6 +39,7 @@ class MvnLogProbFn(torch.autograd.Function):
         return (-0.5 * (quad + logdet + n * LOG2PI)).reshape(batch_shape), info
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, _):
         W, a = ctx.saved_tensors
         Kshape, dshape, batch_shape = ctx.shapes

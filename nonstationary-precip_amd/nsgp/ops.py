@@ -13,6 +13,7 @@ import functools
 from typing import NamedTuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import BackendError
@@ -1319,17 +1320,22 @@ class GibbsKernelFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, x2, ell1, ell2, outputscale, diag_add, nu=None):
-        ctx.save_for_backward(x1, x2, ell1, ell2, outputscale)
+        # a host-number outputscale (gibbs_build takes one) is no variable: it stays in ctx and has no gradient
+        os_t = torch.is_tensor(outputscale)
+        ctx.save_for_backward(x1, x2, ell1, ell2, outputscale if os_t else None)
+        ctx.os_host = None if os_t else outputscale
         ctx.nu = nu
         ctx.has_diag = diag_add is not None
         ctx.diag_shape = diag_add.shape if torch.is_tensor(diag_add) else None
         return gibbs_build(x1, x2, ell1, ell2, outputscale, diag_add, nu=nu)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, G):
         x1, x2, ell1, ell2, outputscale = ctx.saved_tensors
         need_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        g_l1, g_l2, g_x1, g_x2, g_os = gibbs_build_bwd(x1, x2, ell1, ell2, outputscale, G, need_x=need_x, nu=ctx.nu)
+        os_ = outputscale if outputscale is not None else ctx.os_host
+        g_l1, g_l2, g_x1, g_x2, g_os = gibbs_build_bwd(x1, x2, ell1, ell2, os_, G, need_x=need_x, nu=ctx.nu)
         g_diag = None
         if ctx.has_diag and ctx.needs_input_grad[5]:
             g_diag = torch.diagonal(G).sum().reshape(ctx.diag_shape if ctx.diag_shape is not None else ())
@@ -1365,6 +1371,7 @@ class RbfKernelFn(torch.autograd.Function):
         return rbf_build(x1, x2, ls, os_, diag_add)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, G):
         return (*_ard_fn_backward(ctx, rbf_build_bwd, (), G), None)
 
@@ -1379,6 +1386,7 @@ class MaternKernelFn(torch.autograd.Function):
         return matern_build(x1, x2, ls, os_, nu, diag_add)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, G):
         return (*_ard_fn_backward(ctx, matern_build_bwd, (ctx.nu,), G), None, None)
 
@@ -1395,6 +1403,7 @@ class RbfPeriodicKernelFn(torch.autograd.Function):
         return rbf_periodic_build(x1, x2, ls_rbf, ls_per, period, os_, diag_add)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, G):
         x1, x2, ls_per, period, *rest = ctx.saved_tensors
         ls_rbf = rest.pop(0) if ctx.has[0] else None
@@ -1416,6 +1425,7 @@ class Ps2dKernelFn(torch.autograd.Function):
         return ps2d_build(x1, x2, s1, s2, jitter)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, G):
         x1, x2, s1, s2 = ctx.saved_tensors
         g1, g2 = ps2d_build_bwd(x1, x2, s1, s2, ctx.jitter, G)
@@ -1455,6 +1465,8 @@ class MatmulFn(torch.autograd.Function):
                 gA = matmul(B, G, tb, True, b_lower, out_lower, a_lower)
             if A.dim() == 2 and gA.dim() == 3:
                 gA = gA.sum(0)
+            elif A.dim() == 3 and A.shape[0] == 1 and gA.shape[0] > 1:      # batch 1 broadcast against batch nb
+                gA = gA.sum(0, keepdim=True)
         if ctx.needs_input_grad[1]:
             if not tb:
                 gB = matmul(A, G, not ta, False, a_lower, out_lower, b_lower)
@@ -1462,6 +1474,8 @@ class MatmulFn(torch.autograd.Function):
                 gB = matmul(G, A, True, ta, out_lower, a_lower, b_lower)
             if B.dim() == 2 and gB.dim() == 3:
                 gB = gB.sum(0)
+            elif B.dim() == 3 and B.shape[0] == 1 and gB.shape[0] > 1:
+                gB = gB.sum(0, keepdim=True)
         return gA, gB, None, None, None, None, None
 
 
@@ -1486,6 +1500,7 @@ class CholInvFn(torch.autograd.Function):
         return W, info
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, Wbar, _):
         (W,) = ctx.saved_tensors
         Bm = gemm(Wbar, W, False, True, flags=GEMM_A_LOWER | GEMM_B_UPPER)      # tril(Wbar) W^T
@@ -1533,6 +1548,7 @@ class GaussEllFn(torch.autograd.Function):
         return gauss_ell(y, mu, v, noise, scale)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         y, mu, v, noise = ctx.saved_tensors
         gmu, gv, gn = gauss_ell_bwd(y, mu, v, noise, ctx.scale, g, need_noise=ctx.needs_input_grad[3])
@@ -1548,6 +1564,7 @@ class KlWhitenedFn(torch.autograd.Function):
         return kl_whitened(m, Lq).sum()
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         m, Lq = ctx.saved_tensors
         gm, gL = kl_whitened_bwd(m, Lq, 1.0)
@@ -1565,6 +1582,7 @@ class GaussEllTotalFn(torch.autograd.Function):
         return gauss_ell_total(y, mu, v, noise, scale).reshape(())
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         y, mu, v, noise = ctx.saved_tensors
         gmu, gv, gn = gauss_ell_total_bwd(y, mu, v, noise, ctx.scale, g, need_noise=ctx.needs_input_grad[3])
@@ -1583,6 +1601,7 @@ class KlWhitenedTotalFn(torch.autograd.Function):
         return out.reshape(())
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         m, Lq = ctx.saved_tensors
         gm, gL = kl_whitened_total_bwd(m, Lq, ctx.scale, g)
@@ -1602,6 +1621,7 @@ class KlMeanFieldTotalFn(torch.autograd.Function):
         return out.reshape(())
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         m, s2 = ctx.saved_tensors
         gm, gs2 = kl_meanfield_total_bwd(m, s2, ctx.scale, g)
@@ -1649,6 +1669,7 @@ class DsviObjectiveFn(torch.autograd.Function):
         return out.reshape(())
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         ell_scale, kl_scale, ng, shapes = ctx.cfg
         y, mu, v, noise, *rest = ctx.saved_tensors
@@ -1679,6 +1700,7 @@ class DgpSampleFn(torch.autograd.Function):
         return dgp_sample(mean, var, eps)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gh):
         var, eps = ctx.saved_tensors
         gm, gv = dgp_sample_bwd(var, eps, gh)

@@ -19,6 +19,7 @@ folded into a GEMM epilogue and an operand loader) + one batched M^3 Cholesky ad
 import weakref
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from .ops import GEMM_A_LOWER, GEMM_A_UPPER, GEMM_B_LOWER, GEMM_B_UPPER, GEMM_C_LOWER, GEMM_C_NOFILL, GEMM_C_HALFDIAG
@@ -134,6 +135,7 @@ class WhitenFn(torch.autograd.Function):
         return (*outs, info, *[t.view_as(t) for t in flat], *outs64)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, *gouts):
         W64, *flat = ctx.saved_tensors
         ng = len(ctx.sizes)
@@ -312,6 +314,7 @@ class SVGPLayerFn(torch.autograd.Function):
         return mean, var
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gmean, gvar):
         x, Z, ls, os_, m, Lq, W, Kzx, A, C, mean_w, mean_c = ctx.saved_tensors
         if Kzx is None:                                  # fused / float64-Kzx forward: built here, once, for the Wbar product
@@ -381,6 +384,7 @@ class SVGPMeanFieldLayerFn(torch.autograd.Function):
         return mean, var
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gmean, gvar):
         x, Z, ls, os_, m, s2m1, W, Kzx, A, mean_w, mean_c = ctx.saved_tensors
         if Kzx is None:                                  # built here, once, for the Wbar product
