@@ -221,6 +221,26 @@ size_t nsgp_gemm_workspace(int64_t M, int64_t N, int64_t K, int64_t nb1, int64_t
 #define NSGP_GEMM_PLAN_FIELDS 11
 int nsgp_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t nb1, int64_t nb2, int elem_size, int flags,
                    int vec_a, int vec_b, int mode_a, int mode_b, int32_t* out);
+/* Host-side query (no GPU is touched): how ONE WAVE of a float32 gemm_kernel workgroup walks its K loop, computed by the
+ * functions the kernel itself runs (gemm_krange, gemm_hot_range, gemm_wave_sched, gemm_next_seg, gemm_pick_mask in csrc/gemm.hip).
+ * tile_m x tile_n: 128 x 128, 128 x 64 or 64 x 64; epi: fused epilogue (0 plain, 1 column statistics, 2 A-adjoint); ksc: k-scaled
+ * loader; edge: the variant with bounds code (a launch that is not `whole` in nsgp_gemm_plan) -- it keeps the whole-wave schedule,
+ * as the 128 x 64 and 64 x 64 tiles do: identity block map, all MFMA tiles of a wave or none; interior: the workgroup runs its
+ * whole K-tiles through the hot loop (always without bounds code; with it: tile inside M and N, vector-loadable operands);
+ * (bm, bn): tile; wave: 0..3 (wave row = wave >> 1, wave column = wave & 1); [kbeg, kend): the K-slice before the triangular
+ * clip.  K-tiles t are counted from the clipped kbeg, in units of the tile depth (32 for 128-row tiles, 16 for 64 x 64).
+ * out[0..NSGP_GEMM_SCHED_HEAD): 0 TM, 1 TN (MFMA tiles of 32 x 32 per wave), 2..3 the 32-row block of the tile that MFMA tile row
+ *   i covers, 4..5 the 32-column block of MFMA tile column j, 6..9 / 10..13 lo / hi of MFMA tile x = i * TN + j: it has work in
+ *   the K-tiles [lo, hi), 14 nt (K-tiles of the workgroup), 15 h0, 16 h1 (hot range), 17 p0, 18 p1 (its stretch with bare
+ *   staging), 19 the clipped kbeg, 20 number of stretches, 21 bit m set: MFMA mask m exists as a loop copy.
+ * then NSGP_GEMM_SCHED_SEGS records of 4: the stretches of the hot range in order (first K-tile, end, MFMA mask run, bare staging);
+ * then nt records of 4, one per K-tile: the mask of MFMA tiles that have work (bit x), the mask run, 1 if the copy that ran
+ *   masks diagonal blocks as it stages the next tile, and how many times the wave ran the K-tile (1, or the kernel hangs).
+ * cap: int32 slots of out (>= head + 4 * segs + 4 * nt, else -14).  Returns 0, or -(index of the bad argument). */
+#define NSGP_GEMM_SCHED_HEAD 24
+#define NSGP_GEMM_SCHED_SEGS 16
+int nsgp_gemm_wave_schedule(int tile_m, int tile_n, int epi, int ksc, int edge, int flags, int interior, int64_t bm, int64_t bn,
+                            int wave, int64_t kbeg, int64_t kend, int32_t* out, int cap);
 int nsgp_gemm_f32(int64_t M, int64_t N, int64_t K, float alpha,
                   const float* A, int64_t sam, int64_t sak, int64_t sa1, int64_t sa2,
                   const float* B, int64_t sbk, int64_t sbn, int64_t sb1, int64_t sb2,

@@ -228,6 +228,190 @@ constexpr int resident_wg_per_cu(size_t elem_size, bool big, bool narrow) { retu
 // fit.  2 otherwise: the 128-row tiles need up to 256 registers (three of the float64-accumulating one were tried: no faster).
 constexpr int launch_min_wg(size_t elem_size, int bm, int bn) { return (elem_size == 4 && bm == 128 && bn == 64) ? 3 : 2; }
 
+// ---- wave schedule of the float32 K loops ---------------------------------------------------------------------------------
+// Which 32-row / 32-column blocks of the tile a wave owns, in which K-tiles each of its MFMA tiles has work, and how the hot
+// range of the K loop is cut into stretches of one (MFMA mask, staging copy) pair.  Host and device: the kernel takes its
+// cuts and masks from these functions and nsgp_gemm_wave_schedule reports them, so the schedule has one definition
+// (tests/test_gemm_wave_schedule_cpu.py checks it without a GPU).  K-tiles are counted from the workgroup's own kbeg.
+#define NSGP_HD __host__ __device__ __forceinline__
+
+// K range of a workgroup: its K-slice intersected with the triangular support of the operands
+struct KRange { int64_t kbeg, kend; int nt; };
+NSGP_HD KRange gemm_krange(int flags, int64_t m0, int64_t n0, int BM, int BN, int BK, int64_t kbeg, int64_t kend) {
+    if (flags & NSGP_GEMM_A_LOWER) { const int64_t e = m0 + BM; if (e < kend) kend = e; }                 // k <= m
+    if (flags & NSGP_GEMM_A_UPPER) { const int64_t s = m0 / BK * BK; if (s > kbeg) kbeg = s; }            // k >= m
+    if (flags & NSGP_GEMM_B_LOWER) { const int64_t s = n0 / BK * BK; if (s > kbeg) kbeg = s; }            // k >= n
+    if (flags & NSGP_GEMM_B_UPPER) { const int64_t e = n0 + BN; if (e < kend) kend = e; }                 // k <= n
+    if ((flags & NSGP_GEMM_C_LOWER) && (n0 > m0 + BM - 1)) kend = kbeg;
+    return KRange{kbeg, kend, kend > kbeg ? (int)((kend - kbeg + BK - 1) / BK) : 0};
+}
+
+// Hot range [h0, h1) of the K loop (tile t and the tile t + 1 it stages are whole) and, for the ROLL loop, its stretch
+// [p0, p1) whose staged tiles are no diagonal block of a triangular operand (the bare staging copy).
+struct HotRange { int h0, h1, p0, p1; };
+NSGP_HD HotRange gemm_hot_range(int flags, int64_t m0, int64_t n0, int BM, int BN, int BK, int64_t kbeg, int64_t kend, int nt,
+                                bool roll, bool interior, bool f32) {
+    const bool triA = flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER), triB = flags & (NSGP_GEMM_B_LOWER | NSGP_GEMM_B_UPPER);
+    auto regular = [&](int t) {
+        const int64_t k0 = kbeg + (int64_t)t * BK;
+        if (k0 + BK > kend) return false;
+        if (!roll) {
+            if (triA && (k0 < m0 + BM) && (k0 + BK > m0)) return false;
+            if (triB && (k0 < n0 + BN) && (k0 + BK > n0)) return false;
+        }
+        return true;
+    };
+    int r0 = 0, r1 = 0;
+    if (interior) {
+        while (r0 < nt && !regular(r0)) ++r0;
+        r1 = r0;
+        while (r1 < nt && regular(r1)) ++r1;
+    }
+    // float32: h0 == 0 always, so the one-tile-ahead loop exists only behind the hot range.  ROLL: a first tile that is not
+    // whole is the only tile (r0 == nt == 1) -- no hot range then; the k-scaled loader's bare loop masks no diagonal block, so
+    // with a triangular operand (no entry point launches that) the K range starts with tiles it cannot take -- none either.
+    if (f32 && r0 > 0) { r0 = 0; r1 = 0; }
+    HotRange h;
+    h.h0 = r0; h.h1 = r1 - 1 > r0 ? r1 - 1 : r0;
+    h.p0 = h.h0; h.p1 = h.h1;
+    if (roll) {
+        // a diagonal block of A covers k in [m0, m0 + BM), of B k in [n0, n0 + BN): staged tiles whose k range meets them lie
+        // at the ends of the K range (or nowhere)
+        auto first_k = [&](int t) { return kbeg + (int64_t)(t + 1) * BK; };
+        int64_t dlo = INT64_MAX, dhi = INT64_MIN;                    // k range covered by diagonal blocks
+        if (triA) { dlo = m0; dhi = m0 + BM; }
+        if (triB) { if (n0 < dlo) dlo = n0; if (n0 + BN > dhi) dhi = n0 + BN; }
+        if (dhi > dlo) {
+            // staged tile t + 1 is plain iff first_k + BK <= dlo or first_k >= dhi.  With both ends possible the plain stretch
+            // is taken as the longer of the two sides; the rest goes through the masking copy (correct for every tile).
+            int below = h.h0, above = h.h1;                          // tiles [h0, below) are plain below; [above, h1) plain above
+            while (below < h.h1 && first_k(below) + BK <= dlo) ++below;
+            while (above > h.h0 && first_k(above - 1) >= dhi) --above;
+            if (below - h.h0 >= h.h1 - above) { h.p0 = h.h0; h.p1 = below; } else { h.p0 = above; h.p1 = h.h1; }
+        }
+    }
+    return h;
+}
+
+// Block map.  A 128-row tile is 2 x 2 waves and a wave runs TM x TN MFMA tiles of 32 x 32.  Identity: wave row r owns the
+// row blocks {2r, 2r + 1}.  Interleaved: {r, 3 - r} -- against a triangular A, or on the diagonal tile of a lower-only
+// output, the K ranges of the blocks grow with the block index, so both wave rows then carry the same work (identity: wave
+// row 1 has twice the K-tiles of wave row 0 inside the diagonal block and the workgroup waits for it at every barrier).
+// Rows are interleaved for a triangular A alone and for a lower-only output of dense operands, columns for the latter only;
+// everything else keeps the identity map (and still gets per-block masks).  EPI 1 (column statistics) always keeps it: its
+// partial sums run over "this wave's rows", then over the two waves along m, so moving a row to the other wave would re-round them.
+// whole_wave: the previous schedule -- identity map, and all MFMA tiles of a wave share one K range (the hull of their
+// ranges), so a wave runs all of them or none and the hot range is cut at the wave's range ends only.  The 128 x 64 tile
+// (three workgroups per CU under the 168-register cap: measured 1 % slower with per-block masks) and every variant with bounds
+// code (EDGE = 1: more loop copies next to the bounds code spill) stay on it.
+NSGP_HD void gemm_block_policy(int flags, int epi, int TM, int TN, int edge, bool& ilv_r, bool& ilv_c, bool& whole_wave) {
+    const bool triA = flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER), triB = flags & (NSGP_GEMM_B_LOWER | NSGP_GEMM_B_UPPER);
+    const bool cL = flags & NSGP_GEMM_C_LOWER;
+    const bool dense_lower = cL && !triA && !triB;
+    whole_wave = !(TM == 2 && TN == 2) || edge != 0;
+    ilv_r = !whole_wave && epi != 1 && ((triA && !triB && !cL) || dense_lower);
+    ilv_c = !whole_wave && epi != 1 && dense_lower;
+}
+
+template <int TM, int TN> struct WaveSched {
+    int rb[TM], cb[TN];                 // 32-row / 32-column block of the tile that MFMA tile row i / column j covers
+    int lo[TM * TN], hi[TM * TN];       // MFMA tile (i, j), bit i * TN + j: K-tiles [lo, hi) in which it has work (empty: lo == hi)
+};
+template <int TM, int TN>
+NSGP_HD WaveSched<TM, TN> gemm_wave_sched(int wave, bool ilv_r, bool ilv_c, bool whole_wave, int flags, int64_t m0, int64_t n0,
+                                          int MT, int BK, int64_t kbeg, int nt) {
+    WaveSched<TM, TN> s;
+    const int wr = wave >> 1, wc = wave & 1;
+    for (int i = 0; i < TM; ++i) s.rb[i] = (ilv_r && TM == 2) ? (i == 0 ? wr : 3 - wr) : wr * TM + i;
+    for (int j = 0; j < TN; ++j) s.cb[j] = (ilv_c && TN == 2) ? (j == 0 ? wc : 3 - wc) : wc * TN + j;
+    auto end_tile = [&](int64_t x) { const int64_t e = (x - kbeg + BK - 1) / BK; return (int)(e > 0 ? (e < nt ? e : nt) : 0); };   // first t with kbeg + t BK >= x
+    auto beg_tile = [&](int64_t x) { const int64_t b = x > kbeg ? (x - kbeg) / BK : 0; return (int)(b < nt ? b : nt); };          // first t with kbeg + (t + 1) BK > x
+    for (int i = 0; i < TM; ++i)
+        for (int j = 0; j < TN; ++j) {
+            const int64_t R0 = m0 + (int64_t)s.rb[i] * MT, C0 = n0 + (int64_t)s.cb[j] * MT;
+            int lo = 0, hi = nt;
+            if (flags & NSGP_GEMM_A_LOWER) { const int e = end_tile(R0 + MT); if (e < hi) hi = e; }      // k <= row
+            if (flags & NSGP_GEMM_A_UPPER) { const int b = beg_tile(R0); if (b > lo) lo = b; }           // k >= row
+            if (flags & NSGP_GEMM_B_UPPER) { const int e = end_tile(C0 + MT); if (e < hi) hi = e; }      // B(k, n): k <= n
+            if (flags & NSGP_GEMM_B_LOWER) { const int b = beg_tile(C0); if (b > lo) lo = b; }           // k >= n
+            if ((flags & NSGP_GEMM_C_LOWER) && C0 > R0 + MT - 1) hi = lo;                                 // strictly above the diagonal
+            if (hi < lo) hi = lo;
+            s.lo[i * TN + j] = lo; s.hi[i * TN + j] = hi;
+        }
+    if (whole_wave) {                   // one range for the wave: the hull of its non-empty MFMA tiles' ranges
+        int lo = nt, hi = 0;
+        for (int x = 0; x < TM * TN; ++x)
+            if (s.hi[x] > s.lo[x]) { if (s.lo[x] < lo) lo = s.lo[x]; if (s.hi[x] > hi) hi = s.hi[x]; }
+        if (hi < lo) { lo = 0; hi = 0; }
+        for (int x = 0; x < TM * TN; ++x) { s.lo[x] = lo; s.hi[x] = hi; }
+    }
+    return s;
+}
+template <int TM, int TN> NSGP_HD int gemm_mask_at(const WaveSched<TM, TN>& s, int t) {
+    int mk = 0;
+    for (int x = 0; x < TM * TN; ++x) mk |= (s.lo[x] <= t && t < s.hi[x]) ? 1 << x : 0;
+    return mk;
+}
+// MFMA masks that exist as loop copies (bit m of the result: mask m is instantiated).  A K-tile copy is TM x TN x 16 MFMAs
+// plus staging, so only the masks the schedule produces on the launches of the SVGP layer are compiled: whole rows of a
+// triangular A (3, 12), and 5, 12, 13 -- the three patterns of a diagonal tile of a lower-only output under the interleaved
+// map.  Any other mask runs the smallest instantiated mask that contains it (the added blocks multiply the zeros the loader
+// wrote, or belong to the part of a lower-only output that is never read).  gemm_bare_set: the masks whose hot-loop copy
+// also exists with bare staging; the others stage through the masking copy, which is correct for every tile (partial masks
+// next to a triangular operand occur where the staged tiles are diagonal blocks anyway).
+NSGP_HD constexpr int gemm_mask_set(int TM, int TN, int epi, int ksc, int edge) {
+    if (TM * TN > 4) return 0;                                      // (float64 tiles: not scheduled here)
+    if (TM * TN != 4 || edge != 0) return 1 | (1 << ((1 << (TM * TN)) - 1));   // whole_wave: all of the wave's MFMA tiles or none
+    if (epi != 0) return (1 << 0) | (1 << 3) | (1 << 12) | (1 << 15);
+    if (ksc != 0) return (1 << 5) | (1 << 12) | (1 << 13) | (1 << 15);
+    return (1 << 0) | (1 << 3) | (1 << 5) | (1 << 12) | (1 << 13) | (1 << 15);
+}
+NSGP_HD constexpr int gemm_bare_set(int TM, int TN, int epi, int ksc, int edge) {
+    if (TM * TN != 4 || edge != 0) return gemm_mask_set(TM, TN, epi, ksc, edge);
+    if (epi != 0) return 1 << 15;
+    return (1 << 5) | (1 << 12) | (1 << 13) | (1 << 15);
+}
+NSGP_HD constexpr int gemm_pick_mask(int allowed, int nbits, int mask) {
+    const int full = (1 << nbits) - 1;
+    for (int pc = 0; pc < nbits; ++pc)
+        for (int m = 0; m < full; ++m)
+            if (((allowed >> m) & 1) && __builtin_popcount(m) == pc && (mask & ~m) == 0) return m;
+    return full;
+}
+// The stretch of the hot range that starts at K-tile t (h0 <= t < h1): it ends at the next range end or staging cut, so one
+// (mask, staging copy) pair holds for all of it.  te > t always and te <= h1: walking t = te from h0 tiles [h0, h1) exactly once.
+struct Seg { int te, need, run; bool bare; };     // end of the stretch, MFMA tiles with work, mask of the copy that runs, its staging
+template <int TM, int TN> NSGP_HD Seg gemm_next_seg(const WaveSched<TM, TN>& s, const HotRange& h, int t, int masks, int bare_set) {
+    int nx = h.h1;
+    auto cut = [&](int c) { if (c > t && c < nx) nx = c; };
+    cut(h.p0); cut(h.p1);
+    for (int x = 0; x < TM * TN; ++x) { cut(s.lo[x]); cut(s.hi[x]); }
+    const int need = gemm_mask_at<TM, TN>(s, t), run = gemm_pick_mask(masks, TM * TN, need);
+    // (merging neighbouring stretches that run the same copy was tried: the longer scalar walk spilled SGPRs to scratch)
+    return Seg{nx, need, run, t >= h.p0 && t < h.p1 && ((bare_set >> run) & 1)};
+}
+// The one mask of the k-scaled loader's bare hot loop (a loop copy chosen at entry).  A lower-only output of dense operands
+// gives every wave a mask that is the same for all K-tiles: on a diagonal tile the waves run 3 / 2 / 2 / 3 of their four MFMA
+// tiles.  With a triangular operand the ranges would differ per K-tile, and on the whole-wave schedule the previous rule
+// holds: every MFMA tile then.
+template <int TM, int TN> NSGP_HD int gemm_ksc_mask(const WaveSched<TM, TN>& s, int h0, int flags, int masks, bool whole_wave) {
+    const bool tri = flags & (NSGP_GEMM_A_LOWER | NSGP_GEMM_A_UPPER | NSGP_GEMM_B_LOWER | NSGP_GEMM_B_UPPER);
+    const int full = (1 << (TM * TN)) - 1;
+    return (tri || whole_wave) ? full : gemm_pick_mask(masks, TM * TN, gemm_mask_at<TM, TN>(s, h0));
+}
+// run f(integral_constant<mask>) for the instantiated mask that gemm_pick_mask gives (wave-uniform `mask`)
+template <int ALLOWED, int NBITS, int M = 0, typename F>
+__device__ __forceinline__ void gemm_with_mask(int picked, F&& f) {
+    if constexpr (M >= (1 << NBITS) - 1) {
+        f(std::integral_constant<int, (1 << NBITS) - 1>{});
+    } else if constexpr (((ALLOWED >> M) & 1) == 0) {
+        gemm_with_mask<ALLOWED, NBITS, M + 1>(picked, f);
+    } else {
+        if (picked == M) f(std::integral_constant<int, M>{});
+        else gemm_with_mask<ALLOWED, NBITS, M + 1>(picked, f);
+    }
+}
+
 // EPI / KSC: fused epilogue and k-scaled loader, see `struct Epi`.
 template <typename T, int BM, int BN, int BK, int MODE_A, int MODE_B, int EPI = 0, int KSC = 0, int EDGE = 1, int MIX = 0>
 __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_kernel(GemmArgs g, T alpha, const T* __restrict__ A,
@@ -362,14 +546,36 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
     const bool cL = g.flags & NSGP_GEMM_C_LOWER;
 
     // K range of this block: slice intersected with the triangular support
-    int64_t kbeg = slice * g.kper, kend = kbeg + g.kper < g.K ? kbeg + g.kper : g.K;
-    if (aL) { const int64_t e = m0 + BM; if (e < kend) kend = e; }                 // k <= m
-    if (aU) { const int64_t s = m0 / BK * BK; if (s > kbeg) kbeg = s; }            // k >= m
-    if (bL) { const int64_t s = n0 / BK * BK; if (s > kbeg) kbeg = s; }            // k >= n
-    if (bU) { const int64_t e = n0 + BN; if (e < kend) kend = e; }                 // k <= n
-    const bool skip_block = cL && (n0 > m0 + BM - 1);
-    if (skip_block) kend = kbeg;
-    const int nt = kend > kbeg ? (int)((kend - kbeg + BK - 1) / BK) : 0;
+    const int64_t kslice = slice * g.kper;
+    const KRange kr_ = gemm_krange(g.flags, m0, n0, BM, BN, BK, kslice, kslice + g.kper < g.K ? kslice + g.kper : g.K);
+    const int64_t kbeg = kr_.kbeg, kend = kr_.kend;
+    const int nt = kr_.nt;
+    // float32: the wave's block map and per-MFMA-tile K ranges (gemm_wave_sched); float64: the identity map, whole-wave masks
+    constexpr bool SCHED = sizeof(T) == 4;
+    constexpr int MASKS = gemm_mask_set(TM, TN, EPI, KSC, EDGE), BARE_MASKS = gemm_bare_set(TM, TN, EPI, KSC, EDGE);
+    [[maybe_unused]] WaveSched<SCHED ? TM : 1, SCHED ? TN : 1> ws;
+    int ro[TM], co[TN];                               // tile-local first row / column of MFMA tile row i / column j
+    if constexpr (SCHED) {
+        bool ilv_r, ilv_c, whole_wave;
+        gemm_block_policy(g.flags, EPI, TM, TN, EDGE, ilv_r, ilv_c, whole_wave);
+        ws = gemm_wave_sched<TM, TN>(wave, ilv_r, ilv_c, whole_wave, g.flags, m0, n0, MT, BK, kbeg, nt);
+#pragma unroll
+        for (int x = 0; x < TM * TN; ++x) {
+            ws.lo[x] = __builtin_amdgcn_readfirstlane(ws.lo[x]);
+            ws.hi[x] = __builtin_amdgcn_readfirstlane(ws.hi[x]);
+        }
+    }
+    if constexpr (SCHED && TM == 2 && TN == 2 && EDGE == 0) {          // (the only variant whose map can differ from the identity)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) ro[i] = __builtin_amdgcn_readfirstlane(ws.rb[i] * MT);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) co[j] = __builtin_amdgcn_readfirstlane(ws.cb[j] * MT);
+    } else {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) ro[i] = wm0 + i * MT;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) co[j] = wn0 + j * MT;
+    }
 
     typename MF::acc_t acc[TM][TN];
 #pragma unroll
@@ -526,21 +732,21 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
     constexpr int FULLMASK = (1 << (TM * TN)) - 1;
     auto ktile = [&](int buf, bool stage, auto tmask_c, auto masked_c, Frag4<T>* ra, Frag4<TB>* rb, int set = 0) __attribute__((always_inline)) {
         constexpr int tmask = decltype(tmask_c)::value;          // compile-time: a runtime mask makes every MFMA conditional
-        const T* as = &As[buf][kr * LDA + wm0 + mc];             // and hipcc then keeps two copies of the accumulators
-        const T* bs = &Bs[buf][kr * LDB + wn0 + mc];
+        const T* as = &As[buf][kr * LDA + mc];                   // and hipcc then keeps two copies of the accumulators
+        const T* bs = &Bs[buf][kr * LDB + mc];
         T af[2][TM], bf[2][TN];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) af[0][i] = as[i * MT];
+        for (int i = 0; i < TM; ++i) af[0][i] = as[ro[i]];
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bf[0][j] = bs[j * MT];
+        for (int j = 0; j < TN; ++j) bf[0][j] = bs[co[j]];
 #pragma unroll
         for (int ks = 0; ks < NKK; ++ks) {
             const int cur = ks & 1, nxt = cur ^ 1;
             if (ks + 1 < NKK) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i) af[nxt][i] = as[(ks + 1) * KS * LDA + i * MT];
+                for (int i = 0; i < TM; ++i) af[nxt][i] = as[(ks + 1) * KS * LDA + ro[i]];
 #pragma unroll
-                for (int j = 0; j < TN; ++j) bf[nxt][j] = bs[(ks + 1) * KS * LDB + j * MT];
+                for (int j = 0; j < TN; ++j) bf[nxt][j] = bs[(ks + 1) * KS * LDB + co[j]];
             }
             if constexpr (MIX == 2) {
                 static_assert(MIX != 2 || KS0 >= 2, "generated operand: two k-steps ahead of the staging stores");
@@ -561,8 +767,9 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    // MFMA-tile masks.  Block row q = wm0 / MT + i covers rows [m0 + q MT, m0 + (q + 1) MT); block column likewise.
-    int cmask_tile = FULLMASK;                       // lower-only output: tiles strictly above the diagonal are skipped
+    // MFMA-tile masks of the float64 kernels (float32: gemm_mask_at on the wave schedule).  Block row q = wm0 / MT + i covers
+    // rows [m0 + q MT, m0 + (q + 1) MT); block column likewise.
+    int cmask_tile = FULLMASK;                      // lower-only output: tiles strictly above the diagonal are skipped
     if (cL) {
         cmask_tile = 0;
 #pragma unroll
@@ -665,19 +872,10 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
             // results.  Dropped.)
             // ROLL: every float32 product without the k-scaled loader
             constexpr bool ROLL = sizeof(T) == 4 && KSC == 0;
-            auto regular = [&](int t) __attribute__((always_inline)) {
-                const int64_t k0 = kbeg + (int64_t)t * BK;
-                if (k0 + BK > kend) return false;
-                if constexpr (!ROLL) {
-                    if ((aL || aU) && (k0 < m0 + BM) && (k0 + BK > m0)) return false;
-                    if ((bL || bU) && (k0 < n0 + BN) && (k0 + BK > n0)) return false;
-                }
-                return true;
-            };
-            int r0 = 0, r1 = 0;
-            // (waves of a diagonal output tile of a lower-only product take the hot loop too and compute their whole 64 x 64
-            // block: sending them through the one-tile-ahead generic loop to skip the MFMA tiles above the diagonal held
-            // back the whole workgroup -- Wbar = tril(Abar Kzx^T): 482 -> 456 us)
+            // (gemm_hot_range: h0, h1 and the ROLL loop's staging cuts p0, p1)
+            // (waves of a diagonal output tile of a lower-only product take the hot loop too, in the copy of their mask:
+            // sending them through the one-tile-ahead generic loop to skip the MFMA tiles above the diagonal held back the
+            // whole workgroup -- Wbar = tril(Abar Kzx^T): 482 -> 456 us)
             // EDGE = 1 (ragged or unaligned launch): a workgroup whose tile lies inside M and N, on 16-byte aligned
             // operands, still runs its whole K-tiles through the hot loop; only the ragged last K-tile and the boundary
             // workgroups pay for the bounds code (n = 40000 instead of 40960 used to halve the rate of every launch)
@@ -685,22 +883,28 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
             // their hot loop spills, 1365 -> 1485 us at M = 1000, n = 40000)
             const bool interior = EDGE == 0 || (!(MODE_A == 0 && MODE_B == 0) && g.vecA && g.vecB && m0 + BM <= g.M &&
                                                 n0 + BN <= g.N);
-            if (interior) {
-                while (r0 < nt && !regular(r0)) ++r0;
-                r1 = r0;
-                while (r1 < nt && regular(r1)) ++r1;
-            }
-            const int h0 = r0, h1 = r1 - 1 > r0 ? r1 - 1 : r0;             // hot range [h0, h1)
+            HotRange hr = gemm_hot_range(g.flags, m0, n0, BM, BN, BK, kbeg, kend, nt, ROLL, interior, SCHED);
+            hr.h0 = __builtin_amdgcn_readfirstlane(hr.h0); hr.h1 = __builtin_amdgcn_readfirstlane(hr.h1);
+            hr.p0 = __builtin_amdgcn_readfirstlane(hr.p0); hr.p1 = __builtin_amdgcn_readfirstlane(hr.p1);
+            const int h0 = hr.h0, h1 = hr.h1;                                // hot range [h0, h1)
             auto generic_tiles = [&](int tb, int te) __attribute__((always_inline)) {
                 for (int t = tb; t < te; ++t) {
                     const int buf = t & 1;
                     const bool more = t + 1 < nt;
                     if (more) gload(t + 1, ra0, rb0);                      // next tile -> registers (in flight)
-                    const int mk = __builtin_amdgcn_readfirstlane(tile_mask(kbeg + (int64_t)t * BK));
-                    // Two specialisations only -- all MFMA tiles, or none: a partly needed K-tile runs the full set (the
-                    // skipped MFMA tiles only ever multiply the zeros the loader wrote).
-                    if (mk == 0) ktile(buf, more, std::integral_constant<int, 0>{}, std::true_type{}, ra0, rb0);
-                    else ktile(buf, more, std::integral_constant<int, FULLMASK>{}, std::true_type{}, ra0, rb0);
+                    if constexpr (SCHED) {
+                        // the instantiated mask that holds the wave's needed MFMA tiles (gemm_pick_mask)
+                        const int mk = __builtin_amdgcn_readfirstlane(gemm_pick_mask(MASKS, TM * TN, gemm_mask_at<TM, TN>(ws, t)));
+                        gemm_with_mask<MASKS, TM * TN>(mk, [&](auto mc) __attribute__((always_inline)) {
+                            ktile(buf, more, mc, std::true_type{}, ra0, rb0);
+                        });
+                    } else {
+                        const int mk = __builtin_amdgcn_readfirstlane(tile_mask(kbeg + (int64_t)t * BK));
+                        // Two specialisations only -- all MFMA tiles, or none: a partly needed K-tile runs the full set (the
+                        // skipped MFMA tiles only ever multiply the zeros the loader wrote).
+                        if (mk == 0) ktile(buf, more, std::integral_constant<int, 0>{}, std::true_type{}, ra0, rb0);
+                        else ktile(buf, more, std::integral_constant<int, FULLMASK>{}, std::true_type{}, ra0, rb0);
+                    }
                     NSGP_LOOP_BARRIER();
                 }
             };
@@ -708,7 +912,7 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
             sstore(0, ra0, rb0);
             __syncthreads();
             NSGP_STAMP(1);
-            generic_tiles(0, h0);
+            if constexpr (!SCHED) generic_tiles(0, h0);                    // (float32: h0 == 0, gemm_hot_range)
             // float64 tiles are short (BK = 16: 2048 MFMA cycles per K-tile, the staging stores start after 1024): a load
             // issued at the top of a tile has not landed when its first store comes up (wait_any 20 % of wave time).
             // DEPTH2 keeps TWO K-tiles of loads in flight in two register sets: tile t stores the set loaded during tile
@@ -721,25 +925,13 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
                 // its second half, diagonal blocks of triangular operands masked on the way (a uniform branch around the
                 // select code; the MFMA part of the body is the same for every tile).
                 if (h1 > h0) {
-                    // K-tiles [lo, hi) in which THIS WAVE has work: its 64 rows against a triangular A, its columns against a
-                    // triangular B, nothing at all for a wave above the diagonal of a lower-only output.  Outside that range
-                    // the wave stages operands and keeps the barriers but issues no MFMA (a second copy of the loop): its SIMD
-                    // goes to the co-resident workgroup.  (The one-tile-ahead generic loop that used to take the diagonal K-tiles
-                    // ran them 40 % slower than the hot loop: 4 of a tile's 4..32 K-tiles, 8 us of a 92 us workgroup --
-                    // tools/probes/gemm_stamps.py.)
-                    int lo = h0, hi = h1;
-                    {
-                        const int64_t R0 = m0 + wm0, C0 = n0 + wn0;
-                        if (aL) { const int64_t e = (R0 + WM - kbeg + BK - 1) / BK; if (e < hi) hi = (int)(e > 0 ? e : 0); }
-                        if (aU) { const int64_t b = R0 > kbeg ? (R0 - kbeg) / BK : 0; if (b > lo) lo = (int)b; }
-                        if (bU) { const int64_t e = (C0 + WN - kbeg + BK - 1) / BK; if (e < hi) hi = (int)(e > 0 ? e : 0); }
-                        if (bL) { const int64_t b = C0 > kbeg ? (C0 - kbeg) / BK : 0; if (b > lo) lo = (int)b; }
-                        if (cmask_tile == 0) { lo = h0; hi = h0; }
-                        if (lo > h1) lo = h1;
-                        if (hi < lo) hi = lo;
-                        lo = __builtin_amdgcn_readfirstlane(lo);
-                        hi = __builtin_amdgcn_readfirstlane(hi);
-                    }
+                    // Each MFMA tile of the wave has work in the K-tiles [lo, hi) of the wave schedule: its 32 rows against a
+                    // triangular A, its 32 columns against a triangular B, nothing at all above the diagonal of a lower-only
+                    // output.  Outside them the wave stages operands and keeps the barriers but issues no MFMA for that tile
+                    // (a copy of the loop per mask): its SIMD goes to the co-resident workgroup.  EVERY wave runs every K-tile of
+                    // [h0, h1) exactly once, whatever its masks -- the staging stores and the barriers are the workgroup's.
+                    // (The one-tile-ahead generic loop that used to take the diagonal K-tiles ran them 40 % slower than the
+                    // hot loop: 4 of a tile's 4..32 K-tiles, 8 us of a 92 us workgroup -- tools/probes/gemm_stamps.py.)
                     const T* pa = la.cur + (int64_t)(h0 + 1) * BK * la.kstep;
                     const TB* pb = lb.cur + (int64_t)(h0 + 1) * BK * lb.kstep;
                     const int64_t da = (int64_t)BK * la.kstep, db = (int64_t)BK * lb.kstep;
@@ -761,44 +953,25 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
                             NSGP_LOOP_BARRIER();
                         }
                     };
-                    // tiles [p0, p1): the tile they STAGE (t + 1) is no diagonal block -- the bare body, as before; the few
-                    // tiles at either end stage through the masking copy.  Cut [h0, h1) at p0, p1, lo, hi: four copies of
-                    // the loop (MFMAs on / off x masking on / off), picked per stretch.
-                    int p0 = h0, p1 = h1;
-                    {
-                        auto first_k = [&](int t) { return kbeg + (int64_t)(t + 1) * BK; };
-                        // a diagonal block of A covers k in [m0, m0 + BM), of B k in [n0, n0 + BN): staged tiles whose k range meets
-                        // them lie at the ends of the K range (or nowhere)
-                        int64_t dlo = INT64_MAX, dhi = INT64_MIN;                    // k range covered by diagonal blocks
-                        if (aL || aU) { dlo = m0; dhi = m0 + BM; }
-                        if (bL || bU) { if (n0 < dlo) dlo = n0; if (n0 + BN > dhi) dhi = n0 + BN; }
-                        if (dhi > dlo) {
-                            // staged tile t + 1 is plain iff first_k + BK <= dlo or first_k >= dhi.  With both ends possible the plain
-                            // stretch is taken as the longer of the two sides; the rest goes through the masking copy (which is
-                            // correct for every tile).
-                            int below = h0, above = h1;                              // tiles [h0, below) are plain below; [above, h1) plain above
-                            while (below < h1 && first_k(below) + BK <= dlo) ++below;
-                            while (above > h0 && first_k(above - 1) >= dhi) --above;
-                            if (below - h0 >= h1 - above) { p0 = h0; p1 = below; } else { p0 = above; p1 = h1; }
-                        }
-                        p0 = __builtin_amdgcn_readfirstlane(p0);
-                        p1 = __builtin_amdgcn_readfirstlane(p1);
-                    }
-                    int cut[6] = {h0, p0, p1, lo, hi, h1};
-#pragma unroll
-                    for (int a = 1; a < 6; ++a)                                       // insertion sort of six scalars
-#pragma unroll
-                        for (int b = a; b > 0; --b)
-                            if (cut[b] < cut[b - 1]) { const int tmp = cut[b]; cut[b] = cut[b - 1]; cut[b - 1] = tmp; }
+                    // tiles [p0, p1): the tile they STAGE (t + 1) is no diagonal block -- the bare body; the few tiles at either
+                    // end stage through the masking copy.  [h0, h1) is walked in stretches (gemm_next_seg: cut at p0, p1 and at
+                    // the ends of the MFMA tiles' ranges), each in the loop copy of its mask x masking on / off.
+                    int t0 = h0;
 #pragma unroll 1
-                    for (int a = 0; a < 5; ++a) {
-                        const int tb = cut[a], te = cut[a + 1];
-                        if (tb >= te) continue;
-                        const bool active = tb >= lo && te <= hi, plain = tb >= p0 && te <= p1;
-                        if (active && plain) hot_seg(tb, te, std::integral_constant<int, FULLMASK>{}, std::false_type{});
-                        else if (active) hot_seg(tb, te, std::integral_constant<int, FULLMASK>{}, std::true_type{});
-                        else if (plain) hot_seg(tb, te, std::integral_constant<int, 0>{}, std::false_type{});
-                        else hot_seg(tb, te, std::integral_constant<int, 0>{}, std::true_type{});
+                    while (t0 < h1) {
+                        const Seg sg = gemm_next_seg<TM, TN>(ws, hr, t0, MASKS, BARE_MASKS);
+                        const int te = __builtin_amdgcn_readfirstlane(sg.te);
+                        const int mk = __builtin_amdgcn_readfirstlane(sg.run);
+                        if (__builtin_amdgcn_readfirstlane((int)sg.bare) != 0) {
+                            gemm_with_mask<BARE_MASKS, TM * TN>(mk, [&](auto mc) __attribute__((always_inline)) {
+                                hot_seg(t0, te, mc, std::false_type{});
+                            });
+                        } else {
+                            gemm_with_mask<MASKS, TM * TN>(mk, [&](auto mc) __attribute__((always_inline)) {
+                                hot_seg(t0, te, mc, std::true_type{});
+                            });
+                        }
+                        t0 = te;
                     }
                     hend = h1;
                 }
@@ -807,15 +980,24 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
                 const T* pa = la.cur + (int64_t)(h0 + 1) * BK * la.kstep;
                 const TB* pb = lb.cur + (int64_t)(h0 + 1) * BK * lb.kstep;
                 const int64_t da = (int64_t)BK * la.kstep, db = (int64_t)BK * lb.kstep;
-                for (int t = h0; t < h1; ++t) {
+                auto bare = [&](auto mc) __attribute__((always_inline)) {
+                    for (int t = h0; t < h1; ++t) {
 #pragma unroll
-                    for (int p = 0; p < PA; ++p) ra0[p] = ldg4(pa + p * la.pstep);
+                        for (int p = 0; p < PA; ++p) ra0[p] = ldg4(pa + p * la.pstep);
 #pragma unroll
-                    for (int p = 0; p < PB; ++p) rb0[p] = ldg4(pb + p * lb.pstep);
-                    if constexpr (KSC != 0) load_ks(kbeg + (int64_t)(t + 1) * BK);
-                    pa += da; pb += db;
-                    ktile(t & 1, true, std::integral_constant<int, FULLMASK>{}, std::false_type{}, ra0, rb0);
-                    NSGP_LOOP_BARRIER();
+                        for (int p = 0; p < PB; ++p) rb0[p] = ldg4(pb + p * lb.pstep);
+                        if constexpr (KSC != 0) load_ks(kbeg + (int64_t)(t + 1) * BK);
+                        pa += da; pb += db;
+                        ktile(t & 1, true, mc, std::false_type{}, ra0, rb0);
+                        NSGP_LOOP_BARRIER();
+                    }
+                };
+                if constexpr (SCHED && KSC != 0 && TM * TN == 4 && EDGE == 0) {
+                    // float32 128 x 128 without bounds code: one loop copy, chosen here (gemm_ksc_mask)
+                    const int mk = __builtin_amdgcn_readfirstlane(gemm_ksc_mask<TM, TN>(ws, h0, g.flags, MASKS, false));
+                    gemm_with_mask<MASKS, TM * TN>(mk, bare);
+                } else {
+                    bare(std::integral_constant<int, FULLMASK>{});
                 }
                 hend = h1;
             }
@@ -870,11 +1052,11 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int r = 0; r < MF::NREG; ++r) {
-                const int64_t row = m0 + wm0 + i * MT + MF::crow(r, lane);
+                const int64_t row = m0 + ro[i] + MF::crow(r, lane);
                 const T rvv = (rv && row < g.M) ? (T)rv[row] : T(0);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    const int64_t col = n0 + wn0 + j * MT + MF::ccol(lane);
+                    const int64_t col = n0 + co[j] + MF::ccol(lane);
                     const T v = alpha * acc[i][j][r];
                     if (row < g.M && col < g.N) Cb[row * g.ldc + col] = (TC)v;
                     sdot[j] += v * rvv;
@@ -895,7 +1077,7 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
         if (lane < MT) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const int c = wn0 + j * MT + lane;
+                const int c = co[j] + lane;
                 red[(0 + (wave >> 1)) * BN + c] = sdot[j];
                 red[(2 + (wave >> 1)) * BN + c] = ssq[j];
             }
@@ -924,7 +1106,7 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
         const bool inside = (m0 + BM <= g.M) && (n0 + BN <= g.N);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int64_t col = n0 + wn0 + j * MT + MF::ccol(lane);
+            const int64_t col = n0 + co[j] + MF::ccol(lane);
             const int64_t colc = col < g.N ? col : g.N - 1;
             const T gcol = gc[colc], c2 = T(2) * cs[colc];
 #pragma unroll
@@ -933,19 +1115,19 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
                 if (inside) {
 #pragma unroll
                     for (int r = 0; r < MF::NREG; ++r) {
-                        const int64_t row = m0 + wm0 + i * MT + MF::crow(r, lane);
+                        const int64_t row = m0 + ro[i] + MF::crow(r, lane);
                         av[r] = mat[row * g.ldc + col];
                         rvv[r] = rv[row];
                     }
 #pragma unroll
                     for (int r = 0; r < MF::NREG; ++r) {
-                        const int64_t row = m0 + wm0 + i * MT + MF::crow(r, lane);
+                        const int64_t row = m0 + ro[i] + MF::crow(r, lane);
                         Cb[row * g.ldc + col] = (alpha * acc[i][j][r] - av[r]) * c2 + rvv[r] * gcol;
                     }
                 } else {
 #pragma unroll
                     for (int r = 0; r < MF::NREG; ++r) {
-                        const int64_t row = m0 + wm0 + i * MT + MF::crow(r, lane);
+                        const int64_t row = m0 + ro[i] + MF::crow(r, lane);
                         if (row < g.M && col < g.N)
                             Cb[row * g.ldc + col] = (alpha * acc[i][j][r] - mat[row * g.ldc + col]) * c2 + rv[row] * gcol;
                     }
@@ -967,14 +1149,16 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
                             (to_slab || (!cL && beta == T(0) && !(g.flags & NSGP_GEMM_C_HALFDIAG)));
     if (plain_tile) {
         const T sc = to_slab ? T(1) : alpha;
-        T* o0 = out + (m0 + wm0 + MF::crow_lane(lane)) * ldo + n0 + wn0 + MF::ccol(lane);
+        T* o0 = out + (m0 + MF::crow_lane(lane)) * ldo + n0 + MF::ccol(lane);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
+            for (int j = 0; j < TN; ++j) {
+                T* oij = o0 + (int64_t)ro[i] * ldo + co[j];         // the wave's block (i, j) by the block map
 #pragma unroll
-                for (int r = 0; r < MF::NREG; ++r)       // row = the lane's part (in o0) + a compile-time offset
-                    o0[(int64_t)(i * MT + MF::crow_reg(r)) * ldo + j * MT] = sc * acc[i][j][r];
+                for (int r = 0; r < MF::NREG; ++r)       // row = the lane's part (in oij) + a compile-time offset
+                    oij[(int64_t)MF::crow_reg(r) * ldo] = sc * acc[i][j][r];
+            }
         NSGP_STAMP_FLUSH();
         return;
     }
@@ -984,8 +1168,8 @@ __global__ __launch_bounds__(256, launch_min_wg(sizeof(T), BM, BN)) void gemm_ke
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < MF::NREG; ++r) {
-                const int64_t row = m0 + wm0 + i * MT + MF::crow(r, lane);
-                const int64_t col = n0 + wn0 + j * MT + MF::ccol(lane);
+                const int64_t row = m0 + ro[i] + MF::crow(r, lane);
+                const int64_t col = n0 + co[j] + MF::ccol(lane);
                 if (row < g.M && col < g.N) {
                     T v = acc[i][j][r];
                     if (to_slab) {
@@ -1305,6 +1489,63 @@ void gemm_plan_fill(int64_t M, int64_t N, int64_t K, int64_t nb, int flags, int 
     const Order o = plan_order<T>(p, M, N, K, nb, flags, true, vec_a, vec_b, env);
     out[0] = o.bm; out[1] = o.bn; out[2] = (int32_t)p.ksplit; out[3] = (int32_t)p.kper; out[4] = o.whole;
     out[5] = o.xcd_chunk > 0; out[6] = o.batch_perm; out[7] = (int32_t)o.grid_x; out[8] = (int32_t)o.grid_y;
+}
+
+// what nsgp_gemm_wave_schedule reports (include/nsgp.h): one wave's walk through the K loop of a float32 kernel, step for step
+// as gemm_kernel makes it -- generic tiles [0, h0), the hot range in stretches, generic tiles [h1, nt)
+template <int TM, int TN>
+int gemm_wave_schedule_fill(int bm_rows, int bn_cols, int bk, int epi, int ksc, int edge, int flags, int interior, int64_t bm, int64_t bn,
+                            int wave, int64_t kbeg, int64_t kend, int32_t* out, int cap) {
+    constexpr int MT = Mfma<float>::MT;
+    const int64_t m0 = bm * bm_rows, n0 = bn * bn_cols;
+    const KRange kr = gemm_krange(flags, m0, n0, bm_rows, bn_cols, bk, kbeg, kend);
+    const bool roll = ksc == 0;
+    const HotRange hr = gemm_hot_range(flags, m0, n0, bm_rows, bn_cols, bk, kr.kbeg, kr.kend, kr.nt, roll, interior != 0, true);
+    bool ilv_r, ilv_c, whole_wave;
+    gemm_block_policy(flags, epi, TM, TN, edge, ilv_r, ilv_c, whole_wave);
+    const WaveSched<TM, TN> ws = gemm_wave_sched<TM, TN>(wave, ilv_r, ilv_c, whole_wave, flags, m0, n0, MT, bk, kr.kbeg, kr.nt);
+    const int masks = gemm_mask_set(TM, TN, epi, ksc, edge);
+    if (cap < NSGP_GEMM_SCHED_HEAD + 4 * NSGP_GEMM_SCHED_SEGS + 4 * kr.nt) return -14;
+    out[0] = TM; out[1] = TN;
+    for (int i = 0; i < TM; ++i) out[2 + i] = ws.rb[i];
+    for (int j = 0; j < TN; ++j) out[4 + j] = ws.cb[j];
+    for (int x = 0; x < TM * TN; ++x) { out[6 + x] = ws.lo[x]; out[10 + x] = ws.hi[x]; }
+    out[14] = kr.nt; out[15] = hr.h0; out[16] = hr.h1; out[17] = hr.p0; out[18] = hr.p1;
+    out[19] = (int32_t)kr.kbeg; out[21] = masks;
+    int32_t* seg = out + NSGP_GEMM_SCHED_HEAD;
+    int32_t* til = seg + 4 * NSGP_GEMM_SCHED_SEGS;
+    auto run_tile = [&](int t, int run, int masked) {
+        if (t < 0 || t >= kr.nt) return;
+        til[4 * t + 0] = gemm_mask_at<TM, TN>(ws, t); til[4 * t + 1] |= run; til[4 * t + 2] |= masked; til[4 * t + 3] += 1;
+    };
+    auto generic = [&](int tb, int te) {
+        for (int t = tb; t < te; ++t) run_tile(t, gemm_pick_mask(masks, TM * TN, gemm_mask_at<TM, TN>(ws, t)), 1);
+    };
+    int nseg = 0, hend = hr.h0;
+    auto add_seg = [&](int tb, int te, int run, bool plain) {
+        if (nseg < NSGP_GEMM_SCHED_SEGS) { seg[4 * nseg] = tb; seg[4 * nseg + 1] = te; seg[4 * nseg + 2] = run; seg[4 * nseg + 3] = plain; }
+        ++nseg;
+        for (int t = tb; t < te; ++t) run_tile(t, run, !plain);
+    };
+    if (kr.nt > 0) {
+        generic(0, hr.h0);
+        if (hr.h1 > hr.h0) {
+            if (roll) {
+                int t0 = hr.h0;
+                while (t0 < hr.h1 && nseg <= 4 * NSGP_GEMM_SCHED_SEGS) {       // (the bound only keeps a broken walk from spinning)
+                    const Seg sg = gemm_next_seg<TM, TN>(ws, hr, t0, masks, gemm_bare_set(TM, TN, epi, ksc, edge));
+                    add_seg(t0, sg.te, sg.run, sg.bare);
+                    t0 = sg.te;
+                }
+            } else {
+                add_seg(hr.h0, hr.h1, gemm_ksc_mask<TM, TN>(ws, hr.h0, flags, masks, whole_wave), true);
+            }
+            hend = hr.h1;
+        }
+        generic(hend, kr.nt);
+    }
+    out[20] = nseg;
+    return 0;
 }
 
 // ---- the one launch path -------------------------------------------------------------------------------------------------
@@ -1672,6 +1913,24 @@ int nsgp_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t nb1, int64_t nb2, in
     else gemm_plan_fill<double>(M, N, K, nb, flags, vec_a != 0, vec_b != 0, out);
     out[9] = mode_a; out[10] = mode_b;
     return 0;
+}
+
+int nsgp_gemm_wave_schedule(int tile_m, int tile_n, int epi, int ksc, int edge, int flags, int interior, int64_t bm, int64_t bn,
+                            int wave, int64_t kbeg, int64_t kend, int32_t* out, int cap) {
+    const bool t128 = tile_m == 128 && (tile_n == 128 || tile_n == 64), t64 = tile_m == 64 && tile_n == 64;
+    if (!t128 && !t64) return -1;
+    if (epi < 0 || epi > 2) return -3; if ((ksc | 1) != 1) return -4; if ((edge | 1) != 1) return -5;
+    if ((flags & NSGP_GEMM_A_LOWER) && (flags & NSGP_GEMM_A_UPPER)) return -6;
+    if ((flags & NSGP_GEMM_B_LOWER) && (flags & NSGP_GEMM_B_UPPER)) return -6;
+    if (!edge && !interior) return -7;                     // (without bounds code every workgroup is interior)
+    if (bm < 0) return -8; if (bn < 0) return -9; if (wave < 0 || wave > 3) return -10;
+    if (kbeg < 0) return -11; if (kend < kbeg) return -12; if (!out) return -13;
+    if (cap < NSGP_GEMM_SCHED_HEAD + 4 * NSGP_GEMM_SCHED_SEGS) return -14;
+    for (int i = 0; i < cap; ++i) out[i] = 0;
+    const int bk = tile_bk<float>(tile_m, epi == 0 && ksc == 0);
+    if (t64) return gemm_wave_schedule_fill<1, 1>(tile_m, tile_n, bk, epi, ksc, edge, flags, interior, bm, bn, wave, kbeg, kend, out, cap);
+    if (tile_n == 64) return gemm_wave_schedule_fill<2, 1>(tile_m, tile_n, bk, epi, ksc, edge, flags, interior, bm, bn, wave, kbeg, kend, out, cap);
+    return gemm_wave_schedule_fill<2, 2>(tile_m, tile_n, bk, epi, ksc, edge, flags, interior, bm, bn, wave, kbeg, kend, out, cap);
 }
 
 int nsgp_gemm_f32(int64_t M, int64_t N, int64_t K, float alpha, const float* A, int64_t sam, int64_t sak,

@@ -515,6 +515,48 @@ def gemm_plan(A, B, ta=False, tb=False, flags=0, out=None):
     return GemmPlan(*buf)
 
 
+class GemmWaveSchedule(NamedTuple):
+    """One wave's walk through the K loop of a float32 gemm_kernel workgroup (include/nsgp.h, nsgp_gemm_wave_schedule)."""
+    tm: int
+    tn: int
+    row_blocks: tuple      # 32-row block of the tile per MFMA tile row
+    col_blocks: tuple      # 32-column block of the tile per MFMA tile column
+    lo: tuple              # per MFMA tile x = i * tn + j: it has work in the K-tiles [lo[x], hi[x])
+    hi: tuple
+    nt: int
+    h0: int
+    h1: int
+    p0: int
+    p1: int
+    kbeg: int              # after the triangular clip; K-tiles are counted from it
+    masks: int             # bit m: MFMA mask m exists as a loop copy
+    segments: tuple        # stretches of the hot range: (first K-tile, end, mask run, bare staging)
+    tiles: tuple           # per K-tile: (mask needed, mask run, staging masks diagonal blocks, times run)
+
+
+_SCHED_HEAD, _SCHED_SEGS = 24, 16   # NSGP_GEMM_SCHED_HEAD, NSGP_GEMM_SCHED_SEGS (include/nsgp.h)
+
+
+def gemm_wave_schedule(tile_m, tile_n, flags, bm, bn, wave, kbeg, kend, epi=0, ksc=0, edge=False, interior=True):
+    """Host-side only (no GPU): the schedule gemm_kernel<float, tile_m, tile_n, ...> gives wave `wave` of tile (bm, bn) on the
+    K-slice [kbeg, kend), computed by the functions the kernel runs.  edge: the variant with bounds code (ragged or unaligned
+    launch); interior (edge only): the workgroup's tile lies inside M and N on vector-loadable operands."""
+    depth = 32 if tile_m == 128 else 16
+    cap = _SCHED_HEAD + 4 * _SCHED_SEGS + 4 * ((kend - kbeg + depth - 1) // depth + 2)
+    buf = (ctypes.c_int32 * cap)()
+    _lib.call('nsgp_gemm_wave_schedule', int(tile_m), int(tile_n), int(epi), int(ksc), int(bool(edge)), int(flags),
+              int(bool(interior)), int(bm), int(bn), int(wave), int(kbeg), int(kend), ctypes.cast(buf, ctypes.c_void_p), cap)
+    o = list(buf)
+    tm, tn, nt, nseg = o[0], o[1], o[14], o[20]
+    if nseg > _SCHED_SEGS:
+        raise BackendError(f'gemm_wave_schedule: {nseg} stretches')
+    s0, t0 = _SCHED_HEAD, _SCHED_HEAD + 4 * _SCHED_SEGS
+    return GemmWaveSchedule(tm, tn, tuple(o[2:2 + tm]), tuple(o[4:4 + tn]), tuple(o[6:6 + tm * tn]), tuple(o[10:10 + tm * tn]),
+                            nt, o[15], o[16], o[17], o[18], o[19], o[21],
+                            tuple(tuple(o[s0 + 4 * i:s0 + 4 * i + 4]) for i in range(nseg)),
+                            tuple(tuple(o[t0 + 4 * t:t0 + 4 * t + 4]) for t in range(nt)))
+
+
 GEMM_OUT64_UNSPLIT = -64   # NSGP_GEMM_OUT64_UNSPLIT (include/nsgp.h)
 
 
