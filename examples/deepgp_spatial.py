@@ -38,7 +38,7 @@ def run_split(dataset, random_state, args, device):
     torch.manual_seed(random_state)
     likelihood = getattr(args, 'likelihood', 'gaussian')
     model = m.DeepGP(args.layers, train_x.shape, num_inducing=args.inducing,
-                     variational=getattr(args, 'variational', 'cholesky'),
+                     variational=getattr(args, 'variational', 'cholesky'), nu=getattr(args, 'nu', None),
                      likelihood=StudentTLikelihood() if likelihood == 'student_t' else None).to(device)
     mll = DeepApproximateMLL(VariationalELBO(model.likelihood, model, train_x.shape[-2]))
     train_x, train_y, test_x, test_y = (t.to(device) for t in (train_x, train_y, test_x, test_y))
@@ -93,6 +93,8 @@ def main():
     ap.add_argument('--batch', type=int, default=315)
     ap.add_argument('--variational', choices=('cholesky', 'mean_field'), default='cholesky',
                     help="q(u) of every layer: a dense Cholesky factor (the reference) or a diagonal covariance")
+    ap.add_argument('--nu', type=float, choices=(0.5, 1.5, 2.5), default=None,
+                    help="Matern smoothness of every layer's kernel; default: the RBF kernel (the reference)")
     ap.add_argument('--likelihood', choices=('gaussian', 'student_t'), default='gaussian',
                     help="observation model: Gaussian noise (the reference) or the outlier-robust Student-t, whose ELBO "
                          "term is a 20-node Gauss-Hermite sum in torch ops")

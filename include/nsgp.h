@@ -456,6 +456,13 @@ int nsgp_i8_slice_w_f64(const double* W, int64_t batch, int64_t M, void* Wd, dou
 int nsgp_i8_rbf_build_f32(const float* Z, const float* x, int64_t x_batch_stride, const float* ls, const float* os,
                           int64_t batch, int64_t M, int64_t n, int D, int planes, void* Kd, double* kscale, float* Kzx_f32,
                           void* stream);
+/* nsgp_i8_rbf_build_f32 with a Matern radial function, nu = nu2 / 2 in {1/2, 3/2, 5/2}: the entry is os kappa_nu(s) in
+ * float64, kappa_nu exactly what nsgp_matern_build_f64 evaluates (0 distance for s below the normal range, 0 beyond
+ * exponent -745.13, NaN stays NaN); scales, padding, plane layout and Kzx_f32 as above.  A bad argument returns the
+ * negative index of that argument in this signature (nu2: -10); empty sizes return 0 before any launch. */
+int nsgp_i8_matern_build_f32(const float* Z, const float* x, int64_t x_batch_stride, const float* ls, const float* os,
+                             int64_t batch, int64_t M, int64_t n, int D, int nu2, int planes, void* Kd, double* kscale,
+                             float* Kzx_f32, void* stream);
 int nsgp_svgp_tri_gemm_colstats_i8(const void* Wd, const double* wscale, const void* Kd, const double* kscale,
                                    int planes, const float* rowvec, int64_t batch, int64_t M, int64_t n, float* Y,
                                    void* part_dot, void* part_sq, int64_t part_rows, int partials_f64, void* stream);

@@ -36,6 +36,7 @@
 // 227 / 252 VGPRs, no scratch).  With four planes a workgroup walks two column tiles (i8_walk).
 #include <cstdlib>
 #include "common.h"
+#include "radial.h"
 
 namespace {
 
@@ -93,12 +94,23 @@ __global__ __launch_bounds__(256) void i8_slice_w_kernel(const double* __restric
 }
 
 // ---- digit planes of Kzx, evaluated in float64 from the float32 kernel inputs ------------------------------------
-// One thread = one column j and one k-block of 32: K[k][j] = os exp(-1/2 sum_d ((z[k][d] - x[j][d]) / ls[d])^2).
+// One thread = one column j and one k-block of 32: K[k][j] = os kappa(s), s = sum_d ((z[k][d] - x[j][d]) / ls[d])^2, with
+// the radial function kappa a policy: I8Rbf, exp(-s / 2) spelled as this kernel always spelled it (its digits are pinned
+// bit for bit), or I8Matern<NU2>, which IS MaternRadial<NU2>::eval<double> of radial.h -- the function ops.matern_build
+// evaluates in float64: 0 distance below the normal range of s, 0 beyond exponent -745.13, NaN stays NaN.  kappa <= 1
+// up to one ulp (poly e may round above 1): |sc| <= 64 (1 - 2^-53) since 2^e > |os| strictly, so |t| < 64.5 and every
+// digit stays in [-64, 64].
+struct I8Rbf {
+    static __device__ __forceinline__ double eval(double r2) { return t_fexp<double>(-0.5 * r2); }
+};
+template <int NU2> struct I8Matern {
+    static __device__ __forceinline__ double eval(double s) { return MaternRadial<NU2>::template eval<double>(s); }
+};
 // Digit scale: every workgroup (256 columns x one k-block) writes its own slot ksc[b][kb][blockIdx.x] -- os's power of two / 64,
 // or NaN when os or an ls is not finite or one of its entries came out NaN (a NaN z or x).  One writer per slot, so a NaN
 // cannot be overwritten by another workgroup's finite value; the product folds the slots of the k-blocks a tile reads.
-template <int D, int SK>
-__global__ __launch_bounds__(256) void i8_rbf_build_kernel(const float* __restrict__ Z, const float* __restrict__ x, int64_t sx,
+template <typename Radial, int D, int SK>
+__global__ __launch_bounds__(256) void i8_kzx_build_kernel(const float* __restrict__ Z, const float* __restrict__ x, int64_t sx,
                                                            const float* __restrict__ ls, const float* __restrict__ os,
                                                            int64_t M, int64_t n, int64_t np, int64_t KB,
                                                            signed char* __restrict__ Kd, double* __restrict__ ksc,
@@ -140,7 +152,7 @@ __global__ __launch_bounds__(256) void i8_rbf_build_kernel(const float* __restri
                 const bool in = j < n && kb * 32 + kk < M;
                 const bool nan_e = in && r2 != r2;
                 if (nan_e) bad = 1;
-                const double ev = in ? t_fexp<double>(-0.5 * r2) : 0.0;
+                const double ev = in ? Radial::eval(r2) : 0.0;
                 const double evd = nan_e ? 0.0 : ev;          // (no NaN into the digit cutter's float -> int conversions)
                 // the float32 Kzx the backward pass needs for Wbar = tril(Abar Kzx^T), rounded from the float64 value (the
                 // forward pass itself never reads it): saves the backward's own build launch
@@ -421,6 +433,26 @@ static inline int64_t i8_mp(int64_t M) { return cdiv64(M, I8_BM) * I8_BM; }
 static inline int64_t i8_np(int64_t n) { return cdiv64(n, I8_BN) * I8_BN; }
 static inline int64_t i8_kb(int64_t M) { return cdiv64(M, I8_BK); }
 
+// the plane build of one radial function, arguments checked by the caller: D in 1..4, planes in {4, 5}, no empty size
+template <typename Radial>
+int i8_kzx_build_launch(const float* Z, const float* x, int64_t sx, const float* ls, const float* os, int64_t batch, int64_t M,
+                        int64_t n, int D, int planes, void* Kd, double* kscale, float* Kzx_f32, void* stream) {
+    const int64_t np = i8_np(n), KB = i8_kb(M);
+    dim3 grid((unsigned)cdiv64(np, 256), (unsigned)KB, (unsigned)batch);
+    hipStream_t st = (hipStream_t)stream;
+    signed char* kd = (signed char*)Kd;
+#define NSGP_I8_BUILD(DD, SS) hipLaunchKernelGGL((i8_kzx_build_kernel<Radial, DD, SS>), grid, dim3(256), 0, st, Z, x, sx, ls, os, M, n, np, KB, kd, kscale, Kzx_f32)
+    if (planes == 4) {
+        switch (D) { case 1: NSGP_I8_BUILD(1, 4); break; case 2: NSGP_I8_BUILD(2, 4); break; case 3: NSGP_I8_BUILD(3, 4); break;
+                     default: NSGP_I8_BUILD(4, 4); break; }
+    } else {
+        switch (D) { case 1: NSGP_I8_BUILD(1, 5); break; case 2: NSGP_I8_BUILD(2, 5); break; case 3: NSGP_I8_BUILD(3, 5); break;
+                     default: NSGP_I8_BUILD(4, 5); break; }
+    }
+#undef NSGP_I8_BUILD
+    return nsgp_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -456,20 +488,23 @@ int nsgp_i8_rbf_build_f32(const float* Z, const float* x, int64_t x_batch_stride
     if (D < 1 || D > 4) return -9; if (!Kd) return -10; if (!kscale) return -11;
     if (batch == 0 || M == 0 || n == 0) return 0;
     if (batch > 65535 || i8_kb(M) > 65535) return -6;
-    const int64_t np = i8_np(n), KB = i8_kb(M);
-    dim3 grid((unsigned)cdiv64(np, 256), (unsigned)KB, (unsigned)batch);
-    hipStream_t st = (hipStream_t)stream;
-    signed char* kd = (signed char*)Kd;
-#define NSGP_I8_BUILD(DD, SS) hipLaunchKernelGGL((i8_rbf_build_kernel<DD, SS>), grid, dim3(256), 0, st, Z, x, x_batch_stride, ls, os, M, n, np, KB, kd, kscale, Kzx_f32)
-    if (planes == 4) {
-        switch (D) { case 1: NSGP_I8_BUILD(1, 4); break; case 2: NSGP_I8_BUILD(2, 4); break; case 3: NSGP_I8_BUILD(3, 4); break;
-                     default: NSGP_I8_BUILD(4, 4); break; }
-    } else {
-        switch (D) { case 1: NSGP_I8_BUILD(1, 5); break; case 2: NSGP_I8_BUILD(2, 5); break; case 3: NSGP_I8_BUILD(3, 5); break;
-                     default: NSGP_I8_BUILD(4, 5); break; }
+    return i8_kzx_build_launch<I8Rbf>(Z, x, x_batch_stride, ls, os, batch, M, n, D, planes, Kd, kscale, Kzx_f32, stream);
+}
+
+int nsgp_i8_matern_build_f32(const float* Z, const float* x, int64_t x_batch_stride, const float* ls, const float* os,
+                             int64_t batch, int64_t M, int64_t n, int D, int nu2, int planes, void* Kd, double* kscale,
+                             float* Kzx_f32, void* stream) {
+    if (!Z) return -1; if (!x) return -2; if (x_batch_stride < 0) return -3; if (!ls) return -4; if (!os) return -5;
+    if (batch < 0) return -6; if (M < 0 || !nsgp_i8_supported(M > 0 ? M : 1)) return -7; if (n < 0) return -8;
+    if (D < 1 || D > 4) return -9; if (nu2 != 1 && nu2 != 3 && nu2 != 5) return -10;
+    if (planes != 4 && planes != 5) return -11; if (!Kd) return -12; if (!kscale) return -13;
+    if (batch == 0 || M == 0 || n == 0) return 0;
+    if (batch > 65535 || i8_kb(M) > 65535) return -6;
+    switch (nu2) {
+        case 1: return i8_kzx_build_launch<I8Matern<1>>(Z, x, x_batch_stride, ls, os, batch, M, n, D, planes, Kd, kscale, Kzx_f32, stream);
+        case 3: return i8_kzx_build_launch<I8Matern<3>>(Z, x, x_batch_stride, ls, os, batch, M, n, D, planes, Kd, kscale, Kzx_f32, stream);
+        default: return i8_kzx_build_launch<I8Matern<5>>(Z, x, x_batch_stride, ls, os, batch, M, n, D, planes, Kd, kscale, Kzx_f32, stream);
     }
-#undef NSGP_I8_BUILD
-    return nsgp_launch_status();
 }
 
 int nsgp_svgp_tri_gemm_colstats_i8(const void* Wd, const double* wscale, const void* Kd, const double* kscale,

@@ -9,14 +9,15 @@ Reference quirks kept: the hidden layers are ONE tied layer 
 num_layers times, and predict() returns only the last batch's distribution.  Additions (keyword-only,
 defaults reproduce the reference): DeepGP(..., num_inducing=250, tie_layers=True, variational='cholesky');
 variational='mean_field' gives every layer a MeanFieldVariationalDistribution; likelihood=None keeps GaussianLikelihood(),
-an instance (BernoulliLikelihood(), StudentTLikelihood()) is used as given.
+an instance (BernoulliLikelihood(), StudentTLikelihood()) is used as given; nu=None keeps ScaleKernel(RBFKernel) layers,
+nu=0.5 | 1.5 | 2.5 gives every layer ScaleKernel(MaternKernel(nu)), a pair (hidden, last) mixes (either entry may be None).
 """
 import torch
 
 import nsgp.gp as gpytorch
 from nsgp.gp import settings
 from nsgp.gp.distributions import MultivariateNormal, MultitaskMultivariateNormal
-from nsgp.gp.kernels import RBFKernel, ScaleKernel
+from nsgp.gp.kernels import MaternKernel, RBFKernel, ScaleKernel
 from nsgp.gp.likelihoods import GaussianLikelihood
 from nsgp.gp.means import ConstantMean, LinearMean
 from nsgp.gp.models import DeepGPLayer, DeepGP as _DeepGPBase, ExactGP
@@ -28,9 +29,9 @@ VARIATIONAL_DISTRIBUTIONS = {'cholesky': CholeskyVariationalDistribution, 'mean_
 
 class DeepGPHiddenLayer(DeepGPLayer):
     """One whitened SVGP layer: Z ~ randn, q(u) = N(m, Lq Lq^T) -- or N(m, diag(s^2)) with variational='mean_field' --,
-    ScaleKernel(RBF-ARD)."""
+    ScaleKernel(RBF-ARD), or ScaleKernel(Matern-ARD) with nu = 0.5 | 1.5 | 2.5."""
 
-    def __init__(self, input_dims, output_dims, num_inducing=250, mean_type='constant', variational='cholesky'):
+    def __init__(self, input_dims, output_dims, num_inducing=250, mean_type='constant', variational='cholesky', nu=None):
         if variational not in VARIATIONAL_DISTRIBUTIONS:
             raise ValueError(f'variational must be one of {sorted(VARIATIONAL_DISTRIBUTIONS)}, got {variational!r}')
         batch_shape = torch.Size([]) if output_dims is None else torch.Size([output_dims])
@@ -40,8 +41,9 @@ class DeepGPHiddenLayer(DeepGPLayer):
         super().__init__(strategy, input_dims, output_dims)
         self.mean_module = ConstantMean(batch_shape=batch_shape) if mean_type == 'constant' \
             else LinearMean(input_dims)
-        self.covar_module = ScaleKernel(RBFKernel(batch_shape=batch_shape, ard_num_dims=input_dims),
-                                        batch_shape=batch_shape, ard_num_dims=None)
+        base = RBFKernel(batch_shape=batch_shape, ard_num_dims=input_dims) if nu is None \
+            else MaternKernel(nu=nu, batch_shape=batch_shape, ard_num_dims=input_dims)
+        self.covar_module = ScaleKernel(base, batch_shape=batch_shape, ard_num_dims=None)
 
     def forward(self, x):
         """Prior at x (what gpytorch's VariationalStrategy evaluates at [Z; x])."""
@@ -59,17 +61,19 @@ class DeepGPHiddenLayer(DeepGPLayer):
 
 class DeepGP(_DeepGPBase):
     def __init__(self, num_layers, train_x_shape, *, num_inducing=250, tie_layers=True, variational='cholesky',
-                 likelihood=None):
+                 likelihood=None, nu=None):
+        nu = tuple(nu) if isinstance(nu, list) else nu       # (anything else unexpected: MaternKernel's RuntimeError)
+        nu_hidden, nu_last = nu if isinstance(nu, tuple) and len(nu) == 2 else (nu, nu)
         hidden = DeepGPHiddenLayer(input_dims=train_x_shape[-1], output_dims=num_output_dims,
-                                   num_inducing=num_inducing, mean_type='linear', variational=variational)
+                                   num_inducing=num_inducing, mean_type='linear', variational=variational, nu=nu_hidden)
         last = DeepGPHiddenLayer(input_dims=hidden.output_dims, output_dims=None,
-                                 num_inducing=num_inducing, mean_type='constant', variational=variational)
+                                 num_inducing=num_inducing, mean_type='constant', variational=variational, nu=nu_last)
         super().__init__()
         if tie_layers:
             stack = [hidden for _ in range(num_layers)]
         else:
             stack = [hidden] + [DeepGPHiddenLayer(hidden.output_dims, num_output_dims, num_inducing, 'linear',
-                                                  variational=variational)
+                                                  variational=variational, nu=nu_hidden)
                                 for _ in range(num_layers - 1)]
         self.layers = torch.nn.ModuleList(stack)
         self.last_layer = last

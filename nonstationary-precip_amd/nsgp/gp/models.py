@@ -97,6 +97,7 @@ class DeepGPLayer(ApproximateGP):
     """gpytorch.models.deep_gps.DeepGPLayer.__call__ semantics: a MultitaskMVN input is
     sampled through its marginals only, the sample is shared by the layer's output GPs, deterministic
     inputs are expanded to num_likelihood_samples."""
+    dsvi_layer = True          # VariationalStrategy takes ScaleKernel(MaternKernel) in these layers (and only in these)
 
     def __init__(self, variational_strategy, input_dims, output_dims):
         super().__init__(variational_strategy)
@@ -206,7 +207,7 @@ class DeepGP(GP):
                 groups = [s.whiten_group() for s in strategies]
                 Ws, _info, passed, W64s = whiten(groups, settings.variational_cholesky_jitter.value(args[0].dtype),
                                                  settings.chol_bwd_f64.on(), passthrough=True, out_dtype=args[0].dtype,
-                                                 with_f64=True)
+                                                 with_f64=True, nu=[s.nu for s in strategies])
                 if plan is not None:                     # staged backward: the whitening chain's adjoint is its own stage
                     flat = plan.cut(list(Ws) + [t for zlo in passed for t in zlo])
                     Ws, passed = flat[:len(Ws)], [tuple(flat[len(Ws) + 3 * i:len(Ws) + 3 * i + 3])

@@ -14,7 +14,7 @@ from .. import ops
 from ..svgp import svgp_marginal, whiten, VAR_JITTER
 from . import settings
 from .distributions import MultivariateNormal
-from .kernels import RBFKernel, ScaleKernel
+from .kernels import MaternKernel, RBFKernel, ScaleKernel
 from .lazy import CholLazyTensor, DiagLazyTensor
 from .means import ConstantMean, LinearMean, ZeroMean
 from .module import Module
@@ -122,16 +122,33 @@ class VariationalStrategy(_VariationalStrategy):
             if q:
                 m, Lq = m.unsqueeze(0), Lq.unsqueeze(0)
         b, M, D = Z.shape
-        kern = self.model.covar_module
-        if not (isinstance(kern, ScaleKernel) and isinstance(kern.base_kernel, RBFKernel)):
-            raise NotImplementedError('VariationalStrategy on the MI355X path supports ScaleKernel(RBFKernel) '
-                                      '(the only kernel models/dgps.py builds)')
+        kern = self._scaled_stationary_kernel()
         ls = kern.base_kernel.lengthscale.reshape(-1, kern.base_kernel.lengthscale.shape[-1])
         if ls.shape[-1] != D:
             ls = ls.expand(ls.shape[0], D)
         ls = ls.expand(b, D)
         os_ = kern.outputscale.reshape(-1).expand(b)
         return Z, ls, os_, m, Lq
+
+    def _scaled_stationary_kernel(self):
+        """The layer's ScaleKernel(RBFKernel) -- or ScaleKernel(MaternKernel) where the model is a layer of a deep GP
+        (DeepGPLayer.dsvi_layer): the Matern path is built and tested for the DSVI layers; a stand-alone ApproximateGP keeps
+        the refusal it always had (tests/test_gpu_matern.py)."""
+        kern = self.model.covar_module
+        base = getattr(kern, 'base_kernel', None)
+        ok = isinstance(kern, ScaleKernel) and (isinstance(base, RBFKernel) or (
+            isinstance(base, MaternKernel) and getattr(self.model, 'dsvi_layer', False)))
+        if not ok:
+            raise NotImplementedError('VariationalStrategy on the MI355X path supports ScaleKernel(RBFKernel) and, in the layers '
+                                      'of a deep GP (DeepGPLayer), ScaleKernel(MaternKernel) (the kernels models/dgps.py builds), '
+                                      f'not {type(kern).__name__}({type(base).__name__}) in a {type(self.model).__name__}')
+        return kern
+
+    @property
+    def nu(self):
+        """None for an RBF layer, the smoothness (0.5 | 1.5 | 2.5) of a Matern layer."""
+        base = self._scaled_stationary_kernel().base_kernel
+        return base.nu if isinstance(base, MaternKernel) else None
 
     def whiten_group(self):
         """(Z, ls, os) of this layer's GPs for the batched Kzz -> Cholesky -> inverse chain."""
@@ -154,7 +171,7 @@ class VariationalStrategy(_VariationalStrategy):
         mean, var, _info = svgp_marginal(x_flat, Z, ls.contiguous(), os_.contiguous(), m, jitter=jitter,
                                          chol_bwd_f64=settings.chol_bwd_f64.on(), W64=W64, mean_w=mean_w,
                                          mean_c=mean_c, W64f=getattr(self, '_W64f_shared', None) if W64 is not None else None,
-                                         kzx_f64=bool(feeds_next) and settings.hidden_kzx_f64.on(), **q)
+                                         kzx_f64=bool(feeds_next) and settings.hidden_kzx_f64.on(), nu=self.nu, **q)
         if fused:
             return mean, var
         xin = x_flat if b == 1 and self.inducing_points.dim() == 2 else x_flat.unsqueeze(0).expand(b, *x_flat.shape)
@@ -179,15 +196,19 @@ class VariationalStrategy(_VariationalStrategy):
         Kxx + 1e-4 I + C^T C - A^T A per sample, batched GEMMs; no autograd."""
         with torch.no_grad():
             Z, ls, os_, m, Lq = self._flat_params()
+            nu = self.nu
+
+            def build(x1, x2, ls_, o, **kw):
+                return ops.rbf_build(x1, x2, ls_, o, **kw) if nu is None else ops.matern_build(x1, x2, ls_, o, nu, **kw)
             if Z.shape[0] != 1:
                 raise NotImplementedError('full_covariance: single-output layer expected')
             jitter = settings.variational_cholesky_jitter.value(x.dtype)
-            Kzz = ops.rbf_build(Z.double(), Z.double(), ls.double(), os_.double(), diag_add=jitter)
+            Kzz = build(Z.double(), Z.double(), ls.double(), os_.double(), diag_add=jitter)
             L, _ = ops.potrf(Kzz, overwrite=True)
             W64 = ops.trtri(L)[0]
             S, n, D = x.shape
             lsS, osS = ls.expand(S, D).contiguous(), os_.expand(S).contiguous()
-            Kzx = ops.rbf_build(Z[0], x, lsS, osS)                         # (S,M,n)
+            Kzx = build(Z[0], x, lsS, osS)                         # (S,M,n)
             if x.dtype == torch.float32 and settings.whiten_matmul_f64.on():
                 # A = L^-1 Kzx accumulated in float64 like the reference's solve (settings.whiten_matmul_f64); predict
                 # is not a hot path: a plain float64 GEMM on a float64 copy of Kzx
@@ -198,7 +219,7 @@ class VariationalStrategy(_VariationalStrategy):
                 C = Lq[0].sqrt().unsqueeze(-1) * A
             else:
                 C = ops.gemm(Lq[0], A, ta=True, flags=ops.GEMM_A_UPPER)
-            Kxx = ops.rbf_build(x, x, lsS, osS, diag_add=VAR_JITTER)
+            Kxx = build(x, x, lsS, osS, diag_add=VAR_JITTER)
             ops.gemm(C, C, ta=True, beta=1.0, out=Kxx)
             ops.gemm(A, A, ta=True, alpha=-1.0, beta=1.0, out=Kxx)
             return Kxx

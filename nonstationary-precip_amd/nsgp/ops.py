@@ -790,8 +790,9 @@ def _w64_operand(W64f, ref, dims, what):
 
 
 def _kernel_inputs_args(t, ref, what):
-    """(Z, x, ls, os) of an RBF kernel whose Kzx a projection evaluates itself -> the four tensors contiguous (os flat) and
-    (b, M, n), checked: ref's device and dtype, Z:(b,M,D), x:(n,D) or (b,n,D), ls:(b,D), os:(b,)."""
+    """(Z, x, ls, os) of a stationary ARD kernel (RBF; Matern on the int8 path, `kernel_nu`) whose Kzx a projection evaluates
+    itself -> the four tensors contiguous (os flat) and (b, M, n), checked: ref's device and dtype, Z:(b,M,D), x:(n,D) or
+    (b,n,D), ls:(b,D), os:(b,)."""
     if not isinstance(t, (tuple, list)) or len(t) != 4 or not all(isinstance(v, torch.Tensor) for v in t):
         raise BackendError(f'{what}: (Z, x, ls, os) expected')
     _chk(ref, *t)
@@ -812,9 +813,10 @@ def svgp_kzx_fusable(W64f, Z, x, n):
     return bool(_lib.load().nsgp_svgp_kzx_gemm_supported(_p(W64f), M, n, batch, D))
 
 
-def _project_a_i8(W64f, kZ, kx, kls, kos, m, A, part_dot, part_sq, T, p64, planes, flops, kzx_out=None):
+def _project_a_i8(W64f, kZ, kx, kls, kos, m, A, part_dot, part_sq, T, p64, planes, flops, kzx_out=None, nu=None):
     """A = W Kzx as the exact int8 digit-plane product (csrc/gemm_i8.hip): digit planes of W and of Kzx (evaluated in
-    float64 from Z, x, ls, os), then the product with its column-statistic partials (T tile rows per batch element).
+    float64 from Z, x, ls, os -- RBF, or Matern with nu in MATERN_NU), then the product with its column-statistic partials
+    (T tile rows per batch element).
     kzx_out: a list that receives the float32 Kzx (b, M, n) the plane-build kernel writes along (for the backward pass)."""
     lib = _lib.load()
     batch, M, D = kZ.shape
@@ -826,8 +828,12 @@ def _project_a_i8(W64f, kZ, kx, kls, kos, m, A, part_dot, part_sq, T, p64, plane
     ksc = torch.empty((int(lib.nsgp_i8_kscale_count(batch, M, n)),), dtype=torch.float64, device=dev)
     K32 = torch.empty((batch, M, n), dtype=torch.float32, device=dev) if kzx_out is not None else None
     _lib.call('nsgp_i8_slice_w_f64', _p(W64f), batch, M, _p(Wd), _p(wsc), st)
-    _lib.call('nsgp_i8_rbf_build_f32', _p(kZ), _p(kx), n * D if kx.dim() == 3 else 0, _p(kls), _p(kos), batch, M, n, D,
-              planes, _p(Kd), _p(ksc), _p(K32), st)
+    if nu is None:
+        _lib.call('nsgp_i8_rbf_build_f32', _p(kZ), _p(kx), n * D if kx.dim() == 3 else 0, _p(kls), _p(kos), batch, M, n, D,
+                  planes, _p(Kd), _p(ksc), _p(K32), st)
+    else:
+        _lib.call('nsgp_i8_matern_build_f32', _p(kZ), _p(kx), n * D if kx.dim() == 3 else 0, _p(kls), _p(kos), batch, M, n, D,
+                  _nu2(nu), planes, _p(Kd), _p(ksc), _p(K32), st)
     if kzx_out is not None:
         kzx_out.append(K32)
     _timed(lambda: _lib.call('nsgp_svgp_tri_gemm_colstats_i8', _p(Wd), _p(wsc), _p(Kd), _p(ksc), planes, _p(m), batch, M, n,
@@ -894,7 +900,19 @@ def svgp_projection_plan(M, n, batch, dtype, first, second, i8_planes=4):
                           second == 'bf16' and T2 != T)       # the bf16 kernel writes its partials with its own row count
 
 
-def _run_projection(plan, dims, W, B, kin, Lq, m, base, base_add, affine, kzx_out=None):
+def _kernel_nu_arg(kernel_nu, first, what):
+    """kernel_nu of a projection that evaluates Kzx itself: None (RBF), or a Matern nu -- which only the int8 plane build
+    has; the generated-Kzx loader and the bf16 Kxz build are RBF-only paths."""
+    if kernel_nu is None:
+        return None
+    if first != 'i8':
+        raise BackendError(f'{what}: kernel_nu={kernel_nu} needs the int8 product (i8_inputs)' + (
+            f'; the {first!r} projection evaluates Kzx in an RBF-only path' if first in ('kzx_fused', 'bf16') else ''))
+    _nu2(kernel_nu)
+    return float(kernel_nu)
+
+
+def _run_projection(plan, dims, W, B, kin, Lq, m, base, base_add, affine, kzx_out=None, nu=None):
     """Allocate A, C, the partials, mean and var and launch what `plan` says: product 1 (W: its triangular operand in the
     precision the plan's arithmetic reads, B: the Kzx it reads or None, kin: the checked (Z, x, ls, os) it evaluates Kzx
     from or None), the bf16 cast / transpose, product 2 (Lq likewise) and finalize.  Returns A, C, mean, var."""
@@ -923,7 +941,7 @@ def _run_projection(plan, dims, W, B, kin, Lq, m, base, base_add, affine, kzx_ou
                                  T, st), flops, 'f64acc')
     elif plan.first == 'i8':
         _project_a_i8(W, kZ, kx, kls, kos, m, A, part[0], part[1], T, plan.part_dtype != dt, plan.planes, flops,
-                      kzx_out=kzx_out)
+                      kzx_out=kzx_out, nu=nu)
     else:                                                # bf16: bf16 copies of W and of Kxz, written by the build kernel
         Wb = torch.empty((batch, M, M), dtype=torch.bfloat16, device=dev)
         Kxz = torch.empty((batch, n, M), dtype=torch.bfloat16, device=dev)
@@ -959,7 +977,7 @@ def _run_projection(plan, dims, W, B, kin, Lq, m, base, base_add, affine, kzx_ou
 
 
 def svgp_project(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None, kernel_inputs=None, Kzx64=None, Lq64=None,
-                 i8_inputs=None, i8_planes=4, i8_kzx_out=None):
+                 i8_inputs=None, i8_planes=4, i8_kzx_out=None, kernel_nu=None):
     """Fused K6 forward: A = W Kzx, C = Lq^T A (triangular MFMA GEMMs) with the column statistics reduced in
     the GEMM epilogues.  W, Lq:(b,M,M) lower; Kzx:(b,M,n); m:(b,M); base:(b,).
     Returns A, C, mean = A^T m (+ the affine prior mean x w + c, `affine` = (x, w, c)), var = base + base_add +
@@ -971,8 +989,10 @@ def svgp_project(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None, kern
     Kzx64 (float64 (b,M,n), with W64f, instead of Kzx): the same product on a float64 Kzx.  i8_inputs=(Z, x, ls, os) (with
     W64f, instead of Kzx): A on the int8 matrix cores (csrc/gemm_i8.hip), exact int32 accumulation of the digit-plane
     products of the float64 W and of Kzx evaluated in float64 -- 14 with four Kzx planes, 19 with five (`i8_planes`).
-    Lq64 (with Kzx64 or i8_inputs): the float64 Lq -- C is accumulated in float64 too, with float64 partials."""
+    Lq64 (with Kzx64 or i8_inputs): the float64 Lq -- C is accumulated in float64 too, with float64 partials.
+    kernel_nu (with i8_inputs only): the kernel of (Z, x, ls, os) is Matern with that nu instead of RBF."""
     i8, b64 = i8_inputs is not None, Kzx64 is not None
+    kernel_nu = _kernel_nu_arg(kernel_nu, 'i8' if i8 else 'kzx_fused' if kernel_inputs is not None else 'dense', 'svgp_project')
     if i8 and (Kzx is not None or b64 or kernel_inputs is not None or W64f is None):
         raise BackendError('svgp_project: i8_inputs=(Z, x, ls, os) comes with W64f and without Kzx / Kzx64 / kernel_inputs')
     ref = _chk(W, Kzx, Lq, m, base)
@@ -1000,11 +1020,11 @@ def svgp_project(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None, kern
         Lq = _c(Lq64)
     first = 'i8' if i8 else 'f64acc_b64' if b64 else 'kzx_fused' if fused else 'f64acc' if W64f is not None else 'f32'
     plan = svgp_projection_plan(M, n, batch, ref.dtype, first, 'f32' if Lq64 is None else 'f64acc_t', i8_planes)
-    return _run_projection(plan, (batch, M, n), W, B, kin, Lq, m, base, base_add, affine, i8_kzx_out)
+    return _run_projection(plan, (batch, M, n), W, B, kin, Lq, m, base, base_add, affine, i8_kzx_out, kernel_nu)
 
 
 def svgp_project_bf16(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None, kernel_inputs=None, i8_inputs=None,
-                      i8_kzx_out=None):
+                      i8_kzx_out=None, kernel_nu=None):
     """BASELINE configs[4]'s "bf16 forward": the forward projections of a float32 SVGP layer with bf16 matrix-core products
     (bf16 operands, float32 accumulation, float32 A / C; csrc/gemm_bf16.hip), column statistics in the epilogues.
 
@@ -1014,13 +1034,17 @@ def svgp_project_bf16(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None,
         operands are O(1), runs on the bf16 cores from a bf16 transposed copy of A.
     kernel_inputs=(Z, x, ls, os) (forward_precision('bf16_all')): BOTH products in bf16, Kxz written in bf16 by the build
         kernel (nsgp_rbf_build_t_bf16) -- configs[4] to the letter; a throughput figure, not a usable numerical mode.
+    kernel_nu (with i8_inputs only): the kernel of (Z, x, ls, os) is Matern with that nu; the bf16 Kxz build is RBF-only.
     Returns A, C, mean, var (float32).  M must be a multiple of 8."""
+    kernel_nu = _kernel_nu_arg(kernel_nu, 'bf16' if kernel_inputs is not None else 'i8' if i8_inputs is not None else 'dense',
+                               'svgp_project_bf16')
     ref = _chk(Lq, m, base, Kzx)
     if ref.dtype != torch.float32:
         raise BackendError('svgp_project_bf16: float32 layers only')
     if Kzx is None and (i8_inputs is None or W64f is None or kernel_inputs is not None):
         raise BackendError('svgp_project_bf16: Kzx=None needs i8_inputs and W64f (mode bf16)')
     first = 'bf16' if kernel_inputs is not None else 'f32' if W64f is None else 'f64acc' if i8_inputs is None else 'i8'
+    kernel_nu = _kernel_nu_arg(kernel_nu, first, 'svgp_project_bf16')      # (i8_inputs without W64f: not the int8 product)
     kin = dims = None
     if first in ('bf16', 'i8'):
         kin, dims = _kernel_inputs_args(kernel_inputs if first == 'bf16' else i8_inputs, ref, 'svgp_project_bf16')
@@ -1036,7 +1060,7 @@ def svgp_project_bf16(W, Kzx, Lq, m, base, base_add=0.0, affine=None, W64f=None,
         raise BackendError('svgp_project_bf16: shapes')
     plan = svgp_projection_plan(M, n, batch, ref.dtype, first, 'bf16')
     return _run_projection(plan, (batch, M, n), _c(W if W64f is None else W64f), Kzx, kin, Lq, m, base, base_add, affine,
-                           i8_kzx_out)
+                           i8_kzx_out, kernel_nu)
 
 
 def svgp_project_bwd(Lq, m, A, C, gmean, gvar, affine=None):
@@ -1073,12 +1097,14 @@ def svgp_project_bwd(Lq, m, A, C, gmean, gvar, affine=None):
 
 
 def svgp_project_diag(first, W, s2m1, m, base, base_add=0.0, affine=None, Kzx=None, Kzx64=None, kernel_inputs=None,
-                      W64f=None, i8_planes=4, i8_kzx_out=None):
+                      W64f=None, i8_planes=4, i8_kzx_out=None, kernel_nu=None):
     """Forward projection of a layer with a mean-field q(u) = N(m, diag(s^2)): A = W Kzx in the arithmetic `first` names
     (svgp_projection_plan; the operands of `svgp_project` / `svgp_project_bf16`: Kzx for 'f32' / 'f64acc', Kzx64 for
     'f64acc_b64', kernel_inputs = (Z, x, ls, os) for 'kzx_fused' / 'i8' / 'bf16', W64f wherever the float64 W is read),
-    then ONE pass over A instead of the second product.  s2m1:(b,M) = s^2 - 1.
+    then ONE pass over A instead of the second product.  s2m1:(b,M) = s^2 - 1.  kernel_nu (first == 'i8' only): the kernel
+    of kernel_inputs is Matern with that nu; 'kzx_fused' and 'bf16' evaluate Kzx in RBF-only paths.
     Returns A, mean = A^T m (+ the affine prior mean), var = base + base_add + sum_k s2m1_k A_kj^2, summed in float64."""
+    kernel_nu = _kernel_nu_arg(kernel_nu, first, 'svgp_project_diag')
     ref = _chk(W, s2m1, m, base, Kzx)
     needs_w64 = first in ('f64acc', 'f64acc_b64', 'kzx_fused', 'i8')
     if first not in ('f32', 'bf16') and not needs_w64:
@@ -1104,7 +1130,7 @@ def svgp_project_diag(first, W, s2m1, m, base, base_add=0.0, affine=None, Kzx=No
     plan = svgp_projection_plan(M, n, batch, ref.dtype, first, 'diag', i8_planes)
     if first == 'kzx_fused' and not svgp_kzx_fusable(W, kin[0], kin[1], n):
         raise BackendError('svgp_project_diag: the generated-Kzx product needs whole tiles (svgp_kzx_fusable)')
-    A, _, mean, var = _run_projection(plan, (batch, M, n), W, B, kin, s2m1, m, base, base_add, affine, i8_kzx_out)
+    A, _, mean, var = _run_projection(plan, (batch, M, n), W, B, kin, s2m1, m, base, base_add, affine, i8_kzx_out, kernel_nu)
     return A, mean, var
 
 

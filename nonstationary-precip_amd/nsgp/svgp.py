@@ -79,10 +79,28 @@ def _wbar_product(slot, Abar, Kzx):
     return Wbar
 
 
-class WhitenFn(torch.autograd.Function):
-    """W[g] = chol(os_g RBF(Z_g, Z_g; ls_g) + jitter I)^-1 in float64 for a list of GP groups.
+def _kernel_build(nu, x1, x2, ls, os_, **kw):
+    """ops.rbf_build (nu None) or ops.matern_build: the stationary ARD kernel of a layer, chosen by its nu."""
+    return ops.rbf_build(x1, x2, ls, os_, **kw) if nu is None else ops.matern_build(x1, x2, ls, os_, nu, **kw)
 
-    inputs: jitter, chol_bwd_f64, then (Z_i:(b_i,M,D_i), ls_i:(b_i,D_i), os_i:(b_i,)) per group, all with
+
+def _kernel_build_bwd(nu, x1, x2, ls, os_, G, **kw):
+    """The backward of _kernel_build: ops.rbf_build_bwd or ops.matern_build_bwd."""
+    return ops.rbf_build_bwd(x1, x2, ls, os_, G, **kw) if nu is None else ops.matern_build_bwd(x1, x2, ls, os_, nu, G, **kw)
+
+
+def _check_nu(nu, what):
+    if nu is not None and nu not in ops.MATERN_NU:
+        raise ValueError(f'{what}: nu must be None (RBF) or one of {ops.MATERN_NU}, got {nu!r}')
+    return None if nu is None else float(nu)
+
+
+class WhitenFn(torch.autograd.Function):
+    """W[g] = chol(os_g kappa_g(Z_g, Z_g; ls_g) + jitter I)^-1 in float64 for a list of GP groups; kappa_g is RBF, or Matern
+    where the group's entry of `nu` is not None.
+
+    inputs: jitter, chol_bwd_f64, out_dtype, nu (None or one entry per group), then (Z_i:(b_i,M,D_i), ls_i:(b_i,D_i),
+    os_i:(b_i,)) per group, all with
     the same M.  Outputs: W64_i:(b_i, M, M) float64 per group, info:(sum b_i,), then the parameters again
     (Z_i, ls_i, os_i pass-throughs).  A layer that takes its kernel parameters from the pass-throughs sends its Kzx-path
     gradients back through this node, where they join the Kzz-path gradients in one multi-tensor add instead of six
@@ -93,8 +111,9 @@ class WhitenFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, jitter, chol_bwd_f64, out_dtype, *params):
+    def forward(ctx, jitter, chol_bwd_f64, out_dtype, nu, *params):
         groups = [params[i:i + 3] for i in range(0, len(params), 3)]
+        nu = tuple(nu) if nu is not None else (None,) * len(groups)
         z64, off = [], 0
         M = groups[0][0].shape[-2]
         K = torch.empty((sum(g[0].shape[0] for g in groups), M, M), dtype=torch.float64, device=groups[0][0].device)
@@ -108,7 +127,7 @@ class WhitenFn(torch.autograd.Function):
         for gi, (Z, ls, os_) in enumerate(groups):          # Gram matrices straight into the batched buffer
             Zd, lsd, osd = f64[3 * gi:3 * gi + 3]
             z64.append((Zd, lsd, osd))
-            ops.rbf_build(Zd, Zd, lsd, osd, diag_add=jitter, out=K[off:off + Z.shape[0]])
+            _kernel_build(nu[gi], Zd, Zd, lsd, osd, diag_add=jitter, out=K[off:off + Z.shape[0]])
             off += Z.shape[0]
         # K is consumed; the factor itself is never needed.  A float32 model also gets its float32 W from the same launches
         if out_dtype == torch.float32:
@@ -119,6 +138,7 @@ class WhitenFn(torch.autograd.Function):
         ctx.sizes = [g[0].shape[0] for g in groups]
         ctx.dtypes = [g[0].dtype for g in groups]
         ctx.chol_bwd_f64 = chol_bwd_f64
+        ctx.nu = nu
         # float32 layers on a float64 chain: their Wbar products fill the adjoint's float64 buffer themselves
         ctx.wbar_slots = _WbarSlots(W64, ctx.sizes) if (out_dtype == torch.float32 and W64.dtype == torch.float64) else None
         ctx.mark_non_differentiable(info)
@@ -183,7 +203,7 @@ class WhitenFn(torch.autograd.Function):
                 Zk, lsk, osk = Zd.float(), lsd.float(), osd.float()
             else:
                 Zk, lsk, osk = Zd, lsd, osd
-            gZ, _, gls, gos = ops.rbf_build_bwd(Zk, Zk, lsk, osk, Kb.contiguous(), sym=True)   # both sides summed
+            gZ, _, gls, gos = _kernel_build_bwd(ctx.nu[gi], Zk, Zk, lsk, osk, Kb.contiguous(), sym=True)  # both sides summed
             grads += [gZ, gls, gos]
         # back to the parameters' dtypes with ONE multi-tensor copy
         outs = [g if g.dtype == ctx.dtypes[i // 3] else torch.empty(g.shape, dtype=ctx.dtypes[i // 3], device=g.device)
@@ -195,17 +215,23 @@ class WhitenFn(torch.autograd.Function):
         extra = [(o, g) for o, g in zip(outs, gpass) if g is not None]
         if extra:
             torch._foreach_add_([o for o, _ in extra], [g.reshape(o.shape) for o, g in extra])
-        return (None, None, None, *outs)
+        return (None, None, None, None, *outs)
 
 
-def whiten(groups, jitter=1e-4, chol_bwd_f64=True, passthrough=False, out_dtype=None, with_f64=False):
+def whiten(groups, jitter=1e-4, chol_bwd_f64=True, passthrough=False, out_dtype=None, with_f64=False, nu=None):
     """groups: list of (Z:(b,M,D), ls:(b,D), os:(b,)).  Returns (list of W:(b,M,M) per group -- float64 unless
     `out_dtype` asks for the layers' dtype --, info); with
     passthrough=True also the list of (Z, ls, os) pass-through triples a layer should build its Kzx from (WhitenFn);
     with_f64=True appends the list of float64 W per group (non-differentiable companions of the float32 W: the forward
-    projection of a float32 layer accumulates in float64 with them, settings.whiten_matmul_f64)."""
+    projection of a float32 layer accumulates in float64 with them, settings.whiten_matmul_f64).
+    nu: None (every group RBF) or one entry per group, None | 0.5 | 1.5 | 2.5 -- RBF and Matern groups share the chain."""
     flat = [t for g in groups for t in g]
-    res = WhitenFn.apply(float(jitter), bool(chol_bwd_f64), out_dtype, *flat)
+    if nu is not None:
+        if len(nu) != len(groups):
+            raise ValueError(f'whiten: nu needs one entry per group ({len(groups)}), got {len(nu)}')
+        nu = tuple(_check_nu(v, 'whiten') for v in nu)
+        nu = nu if any(v is not None for v in nu) else None
+    res = WhitenFn.apply(float(jitter), bool(chol_bwd_f64), out_dtype, nu, *flat)
     ng = len(groups)
     Ws, info, rest, W64s = res[:ng], res[ng], res[ng + 1:ng + 1 + 3 * ng], res[ng + 1 + 3 * ng:]
     from .gp import settings
@@ -259,6 +285,15 @@ def select_projection(dtype, M, D, n, kzx_f64, has_w64, fusable, forward_precisi
     return first, second, 5 if (kzx_f64 and not bf16) else 4, bool(w64)
 
 
+def _forward_precision_for(nu):
+    """forward_precision('bf16_all') writes Kxz with the RBF-only bf16 build and exists to time BASELINE configs[4]: a
+    Matern layer under it is an error, not a quiet downgrade that would falsify the timing."""
+    from .gp import settings
+    if nu is not None and settings.forward_precision.value() == 'bf16_all':
+        raise NotImplementedError("forward_precision('bf16_all') times the RBF-only bf16 Kxz build: a Matern layer "
+                                  f"(nu={nu}) takes 'f32' or 'bf16'")
+
+
 class SVGPLayerFn(torch.autograd.Function):
     """(x, Z, ls, os, m, Lq, W64, mean_w, mean_c) -> (mean:(b,n), var:(b,n))
 
@@ -273,14 +308,16 @@ class SVGPLayerFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, Z, ls, os_, m, Lq, W64, mean_w, mean_c, W64f=None, kzx_f64=False):
+    def forward(ctx, x, Z, ls, os_, m, Lq, W64, mean_w, mean_c, W64f=None, kzx_f64=False, nu=None):
         from .gp import settings
+        _forward_precision_for(nu)
         W = W64 if W64.dtype == x.dtype else ops.cast(W64, x.dtype)
         if W64f is None and W64.dtype == torch.float64 and x.dtype == torch.float32:
             W64f = W64
         first, second, planes, w64 = select_projection(
             x.dtype, Z.shape[-2], Z.shape[-1], x.shape[-2], kzx_f64, W64f is not None,
-            settings.fuse_kzx.on() and ops.svgp_kzx_fusable(W64f, Z, x, x.shape[-2]), settings.forward_precision.value(),
+            nu is None and settings.fuse_kzx.on() and ops.svgp_kzx_fusable(W64f, Z, x, x.shape[-2]),
+            settings.forward_precision.value(),
             settings.whiten_matmul_f64.on(), settings.whiten_matmul_i8.on(), settings.fuse_kzx.on(), settings.hidden_var_f64.value())
         W64f = W64f if w64 else None
         affine = None if (mean_w is None and mean_c is None) else (x, mean_w, mean_c)
@@ -289,16 +326,16 @@ class SVGPLayerFn(torch.autograd.Function):
             src = [x.detach(), Z.detach(), ls.detach(), os_.detach()] + ([Lq.detach()] if second == 'f64acc_t' else [])
             dst = [torch.empty(t.shape, dtype=torch.float64, device=t.device) for t in src]
             torch._foreach_copy_(dst, src)
-            Kzx64 = ops.rbf_build(dst[1], dst[0], dst[2], dst[3])
+            Kzx64 = _kernel_build(nu, dst[1], dst[0], dst[2], dst[3])
             Lq64 = dst[4] if len(dst) == 5 else None
         elif second == 'f64acc_t':
             Lq64 = ops.cast(Lq.detach(), torch.float64)
         elif first in ('f32', 'f64acc', 'bf16'):       # ('bf16' builds its own bf16 Kxz; it takes this one's shape)
-            Kzx = ops.rbf_build(Z, x, ls, os_)           # (b,M,n)
+            Kzx = _kernel_build(nu, Z, x, ls, os_)       # (b,M,n)
         # int8 path: the plane-build kernel also writes the float32 Kzx the BACKWARD needs (Wbar = tril(Abar Kzx^T)) when there
         # is going to be one -- its own build launch (28 us at the headline's last layer) disappears
         kin = (Z, x, ls, os_)
-        i8 = dict(i8_inputs=kin, i8_kzx_out=[] if any(ctx.needs_input_grad) else None) if first == 'i8' else {}
+        i8 = dict(i8_inputs=kin, i8_kzx_out=[] if any(ctx.needs_input_grad) else None, kernel_nu=nu) if first == 'i8' else {}
         if second == 'bf16':
             A, C, mean, var = ops.svgp_project_bf16(W, Kzx, Lq, m, os_, base_add=VAR_JITTER, affine=affine, W64f=W64f,
                                                     kernel_inputs=kin if first == 'bf16' else None, **i8)
@@ -310,6 +347,7 @@ class SVGPLayerFn(torch.autograd.Function):
             Kzx = i8['i8_kzx_out'][0]
         ctx.save_for_backward(x, Z, ls, os_, m, Lq, W, Kzx, A, C, mean_w, mean_c)
         ctx.w_dtype = W64.dtype
+        ctx.nu = nu
         ctx.wbar_slot = _WbarSlots.find(W64f, W64)
         return mean, var
 
@@ -318,7 +356,7 @@ class SVGPLayerFn(torch.autograd.Function):
     def backward(ctx, gmean, gvar):
         x, Z, ls, os_, m, Lq, W, Kzx, A, C, mean_w, mean_c = ctx.saved_tensors
         if Kzx is None:                                  # fused / float64-Kzx forward: built here, once, for the Wbar product
-            Kzx = ops.rbf_build(Z, x, ls, os_)
+            Kzx = _kernel_build(ctx.nu, Z, x, ls, os_)
         gmean = gmean.contiguous()
         affine = None if (mean_w is None and mean_c is None) else (x, mean_w, mean_c)
         Abar, Lqbar, mbar, basebar, wbar, cbar = ops.svgp_project_bwd(Lq, m, A, C, gmean, gvar.contiguous(),
@@ -326,7 +364,7 @@ class SVGPLayerFn(torch.autograd.Function):
         Kzxbar = ops.gemm(W, Abar, ta=True, flags=GEMM_A_UPPER)                  # W^T Abar
         Wbar = _wbar_product(ctx.wbar_slot, Abar, Kzx)                           # tril(Abar Kzx^T)
         need_x = ctx.needs_input_grad[0]
-        gZ, gx, gls, gos = ops.rbf_build_bwd(Z, x, ls, os_, Kzxbar, need_x1=True, need_x2=need_x)
+        gZ, gx, gls, gos = _kernel_build_bwd(ctx.nu, Z, x, ls, os_, Kzxbar, need_x1=True, need_x2=need_x)
         gos = gos + basebar
         if need_x:
             if mean_w is not None:                       # d(prior mean)/dx = w  (deeper layers of a tied stack only)
@@ -336,7 +374,7 @@ class SVGPLayerFn(torch.autograd.Function):
         return (gx if need_x else None, gZ, gls.reshape(ls.shape), gos.reshape(os_.shape), mbar, Lqbar,
                 Wbar if Wbar.dtype == ctx.w_dtype else ops.cast(Wbar, ctx.w_dtype),
                 None if mean_w is None else wbar.reshape(mean_w.shape),
-                None if mean_c is None else cbar.reshape(mean_c.shape), None, None)
+                None if mean_c is None else cbar.reshape(mean_c.shape), None, None, None)
 
 
 class SVGPMeanFieldLayerFn(torch.autograd.Function):
@@ -351,14 +389,16 @@ class SVGPMeanFieldLayerFn(torch.autograd.Function):
     float64-Kzx forward passes leave it to the backward to build."""
 
     @staticmethod
-    def forward(ctx, x, Z, ls, os_, m, s2, W64, mean_w, mean_c, W64f=None, kzx_f64=False):
+    def forward(ctx, x, Z, ls, os_, m, s2, W64, mean_w, mean_c, W64f=None, kzx_f64=False, nu=None):
         from .gp import settings
+        _forward_precision_for(nu)
         W = W64 if W64.dtype == x.dtype else ops.cast(W64, x.dtype)
         if W64f is None and W64.dtype == torch.float64 and x.dtype == torch.float32:
             W64f = W64
         first, _, planes, w64 = select_projection(
             x.dtype, Z.shape[-2], Z.shape[-1], x.shape[-2], kzx_f64, W64f is not None,
-            settings.fuse_kzx.on() and ops.svgp_kzx_fusable(W64f, Z, x, x.shape[-2]), settings.forward_precision.value(),
+            nu is None and settings.fuse_kzx.on() and ops.svgp_kzx_fusable(W64f, Z, x, x.shape[-2]),
+            settings.forward_precision.value(),
             settings.whiten_matmul_f64.on(), settings.whiten_matmul_i8.on(), settings.fuse_kzx.on(), settings.hidden_var_f64.value(),
             diag_q=True)
         W64f = W64f if w64 else None
@@ -368,18 +408,20 @@ class SVGPMeanFieldLayerFn(torch.autograd.Function):
             src = [x.detach(), Z.detach(), ls.detach(), os_.detach()]
             dst = [torch.empty(t.shape, dtype=torch.float64, device=t.device) for t in src]
             torch._foreach_copy_(dst, src)
-            Kzx64 = ops.rbf_build(dst[1], dst[0], dst[2], dst[3])
+            Kzx64 = _kernel_build(nu, dst[1], dst[0], dst[2], dst[3])
         elif first in ('f32', 'f64acc'):
-            Kzx = ops.rbf_build(Z, x, ls, os_)           # (b,M,n)
+            Kzx = _kernel_build(nu, Z, x, ls, os_)       # (b,M,n)
         kzx_out = [] if (first == 'i8' and any(ctx.needs_input_grad)) else None
         s2m1 = s2.detach() - 1.0
         A, mean, var = ops.svgp_project_diag(first, W, s2m1, m, os_, base_add=VAR_JITTER, affine=affine, Kzx=Kzx, Kzx64=Kzx64,
                                              kernel_inputs=(Z, x, ls, os_) if first in ('kzx_fused', 'i8', 'bf16') else None,
-                                             W64f=W64f, i8_planes=planes, i8_kzx_out=kzx_out)
+                                             W64f=W64f, i8_planes=planes, i8_kzx_out=kzx_out,
+                                             kernel_nu=nu if first == 'i8' else None)
         if kzx_out:
             Kzx = kzx_out[0]
         ctx.save_for_backward(x, Z, ls, os_, m, s2m1, W, Kzx, A, mean_w, mean_c)
         ctx.w_dtype = W64.dtype
+        ctx.nu = nu
         ctx.wbar_slot = _WbarSlots.find(W64f, W64)
         return mean, var
 
@@ -388,14 +430,14 @@ class SVGPMeanFieldLayerFn(torch.autograd.Function):
     def backward(ctx, gmean, gvar):
         x, Z, ls, os_, m, s2m1, W, Kzx, A, mean_w, mean_c = ctx.saved_tensors
         if Kzx is None:                                  # built here, once, for the Wbar product
-            Kzx = ops.rbf_build(Z, x, ls, os_)
+            Kzx = _kernel_build(ctx.nu, Z, x, ls, os_)
         gmean = gmean.contiguous()
         affine = None if (mean_w is None and mean_c is None) else (x, mean_w, mean_c)
         Abar, mbar, s2bar, basebar, wbar, cbar = ops.svgp_project_diag_bwd(m, s2m1, A, gmean, gvar.contiguous(), affine=affine)
         Kzxbar = ops.gemm(W, Abar, ta=True, flags=GEMM_A_UPPER)                  # W^T Abar
         Wbar = _wbar_product(ctx.wbar_slot, Abar, Kzx)                           # tril(Abar Kzx^T)
         need_x = ctx.needs_input_grad[0]
-        gZ, gx, gls, gos = ops.rbf_build_bwd(Z, x, ls, os_, Kzxbar, need_x1=True, need_x2=need_x)
+        gZ, gx, gls, gos = _kernel_build_bwd(ctx.nu, Z, x, ls, os_, Kzxbar, need_x1=True, need_x2=need_x)
         gos = gos + basebar
         if need_x:
             if mean_w is not None:                       # d(prior mean)/dx = w  (deeper layers of a tied stack only)
@@ -405,23 +447,25 @@ class SVGPMeanFieldLayerFn(torch.autograd.Function):
         return (gx if need_x else None, gZ, gls.reshape(ls.shape), gos.reshape(os_.shape), mbar, s2bar,
                 Wbar if Wbar.dtype == ctx.w_dtype else ops.cast(Wbar, ctx.w_dtype),
                 None if mean_w is None else wbar.reshape(mean_w.shape),
-                None if mean_c is None else cbar.reshape(mean_c.shape), None, None)
+                None if mean_c is None else cbar.reshape(mean_c.shape), None, None, None)
 
 
 def svgp_marginal(x, Z, ls, os_, m, Lq=None, jitter=1e-4, chol_bwd_f64=True, W64=None, mean_w=None, mean_c=None, W64f=None,
-                  kzx_f64=False, s2=None):
+                  kzx_f64=False, s2=None, nu=None):
     """mean and variance of q(f) at x for b whitened SVGPs; the mean excludes the prior mean function unless its
     affine parameters are passed (mean_w: LinearMean weights (D,) / (b,D), mean_c: constant or bias (1,) / (b,)).
     q(u) = N(m, Lq Lq^T), or mean-field N(m, diag(s2)) when s2:(b,M) is given in place of Lq.
+    nu: None for the RBF kernel, or 0.5 | 1.5 | 2.5 for Matern (with W64 given, the nu that chain was whitened with).
     Returns (mean, var, info); pass W64 (from `whiten`) to share one factorisation chain across layers."""
+    nu = _check_nu(nu, 'svgp_marginal')
     if (Lq is None) == (s2 is None):
         raise ValueError('svgp_marginal: exactly one of Lq (Cholesky q(u)) and s2 (mean-field q(u)) expected')
     info = None
     if W64 is None:
         (W64,), info, ((Z, ls, os_),), (W64f,) = whiten([(Z, ls, os_)], jitter, chol_bwd_f64, passthrough=True,
-                                                        out_dtype=x.dtype, with_f64=True)
+                                                        out_dtype=x.dtype, with_f64=True, nu=[nu])
     if s2 is not None:
-        mean, var = SVGPMeanFieldLayerFn.apply(x, Z, ls, os_, m, s2, W64, mean_w, mean_c, W64f, kzx_f64)
+        mean, var = SVGPMeanFieldLayerFn.apply(x, Z, ls, os_, m, s2, W64, mean_w, mean_c, W64f, kzx_f64, nu)
     else:
-        mean, var = SVGPLayerFn.apply(x, Z, ls, os_, m, Lq, W64, mean_w, mean_c, W64f, kzx_f64)
+        mean, var = SVGPLayerFn.apply(x, Z, ls, os_, m, Lq, W64, mean_w, mean_c, W64f, kzx_f64, nu)
     return mean, var, info
