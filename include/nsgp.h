@@ -184,6 +184,30 @@ int nsgp_ps2d_build_bwd_f64(const double* x1, const double* x2, const double* si
                             double* g_sig1, double* g_sig2, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K3' Paciorek-Schervish kernel with the Matern radial function (Paciorek & Schervish 2006, full 2x2 Sigma(x)):
+ *     K[i,j] = |S1_i|^(1/4) |S2_j|^(1/4) |A|^(-1/2) * k_nu(sqrt(2 Q)),   A = (S1_i+S2_j)/2,
+ *              Q = d^T (A + jitter I)^-1 d,   d = x1_i - x2_j,   k_nu as K2''
+ *     (K3 is the same expression with e^{-Q} for k_nu(sqrt(2 Q)); S = diag(2 ell^2) and jitter = 0 give K1'.)
+ *     The K3 signatures with nu2 = 2 nu in {1, 3, 5} after n2 (any other value: argument 7 invalid); layouts, the
+ *     outputs of the backward and its summing mode are K3's, and the backward takes its workspace size from
+ *     nsgp_ps2d_build_bwd_workspace.  S is not assumed symmetric; Q < 0 (S not positive definite) is evaluated as
+ *     Q = 0, a NaN stays NaN.  For nu = 1/2 the derivative at zero distance is taken as 0, as in K2''.
+ *     An empty problem (n1 or n2 = 0) returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------ */
+int nsgp_ps2d_matern_build_fwd_f32(const float* x1, const float* x2, const float* sig1, const float* sig2,
+                                   int64_t n1, int64_t n2, int nu2, float jitter, float* K, int64_t ldk,
+                                   void* stream);
+int nsgp_ps2d_matern_build_fwd_f64(const double* x1, const double* x2, const double* sig1, const double* sig2,
+                                   int64_t n1, int64_t n2, int nu2, double jitter, double* K, int64_t ldk,
+                                   void* stream);
+int nsgp_ps2d_matern_build_bwd_f32(const float* x1, const float* x2, const float* sig1, const float* sig2,
+                                   int64_t n1, int64_t n2, int nu2, float jitter, const float* G, int64_t ldg,
+                                   float* g_sig1, float* g_sig2, void* ws, size_t ws_bytes, void* stream);
+int nsgp_ps2d_matern_build_bwd_f64(const double* x1, const double* x2, const double* sig1, const double* sig2,
+                                   int64_t n1, int64_t n2, int nu2, double jitter, const double* G, int64_t ldg,
+                                   double* g_sig1, double* g_sig2, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dense contraction on the matrix cores (v_mfma_f32_32x32x2_f32 / v_mfma_f64_16x16x4_f64)
  *     C[b] = alpha * op(A[b]) * op(B[b]) + beta * C[b]        (M x N, inner K)
  *     replaces the torch matmul / triangular_solve / inverse chains of

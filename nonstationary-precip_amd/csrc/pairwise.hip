@@ -1,7 +1,8 @@
 // pairwise.hip -- kernel-matrix builds K[i,j] = k(row_i, col_j) and their backward reductions.
 //
 //   K1 Gibbs (models/gibbs_kernels.py:154-162), K1' its Matern form (GibbsRadialOp), K2 batched RBF-ARD (gpytorch ScaleKernel(RBF),
-//   models/dgps.py:44-46), K3 Paciorek-Schervish D=2 (models/multivariate_gibbs_kernel.py:98-150).
+//   models/dgps.py:44-46), K3 Paciorek-Schervish D=2 (models/multivariate_gibbs_kernel.py:98-150), K3' its Matern form
+//   (PsRadialOp).
 //
 // Layout: a functor per kernel family (GibbsOp, ArdOp, RbfPeriodicOp, PsOp) is plugged into ONE forward tile kernel and
 // ONE backward tile kernel; dispatch_dim is the one place where the runtime D picks the specialised or generic functor.
@@ -371,6 +372,78 @@ template <typename T> struct PsOp {
         ra[2] += w * (sh2 - dr * r.s[1]); ra[3] += w * (sh3 + dr * r.s[0]);
         ca[0] += w * (sh0 + dc * c.s[3]); ca[1] += w * (sh1 - dc * c.s[2]);
         ca[2] += w * (sh2 - dc * c.s[1]); ca[3] += w * (sh3 + dc * c.s[0]);
+    }
+};
+
+// K3' Paciorek & Schervish (2006) with a full per-point 2x2 Sigma(x) and the Matern radial function:  k = P * kappa(s),
+// PsOp's prefactor P = |S1|^(1/4) |S2|^(1/4) |A|^(-1/2) times the stationary radial function at the squared distance
+// s = 2 Q, Q = delta^T B^-1 delta, A = (S1 + S2) / 2, B = A + jit I (kappa = e^{-s/2} = e^{-Q} is PsOp itself; the Matern
+// argument is d = sqrt(2 Q), P&S's 2 sqrt(nu Q) = sqrt(2 nu) d).  A sibling of PsOp as GibbsRadialOp is of GibbsOp: the
+// per-point operands (P, load, row, col, fcol) and the accumulator layout are inherited, so the launchers, the OutDesc
+// wiring and the workspace size are PsOp's, and PsOp's own code is not touched.  Sigma is not assumed symmetric, the
+// jitter enters the inverse only, and Q < 0 (a Sigma that is not positive definite) is evaluated as Q = 0: k = P, and the
+// distance term of the gradient is dropped; a NaN stays NaN (the test is false for it).
+// Per entry: one reciprocal (det B), one rsqrt (det A), one distance (matern_dist) and one exp (matern_poly_exp).
+// With phi = (d kappa / d d) / d as the policy returns it, u = B^-T delta, v = B^-1 delta:
+//   dk/dS1 = P [kappa (S1^-T - A^-T) / 4 - phi u v^T / 2],   S2 alike with S2^-T.
+template <typename T, typename Radial> struct PsRadialOp : PsOp<T> {
+    using P = typename PsOp<T>::P;
+    static_assert(!Radial::negated, "the policy writes phi");
+    // P (returned), s and the 2x2 pieces of one entry: ONE statement for eval and grad
+    struct Pieces { T a[4]; T b0, b3, d0, d1, iB, detA; bool neg; };
+    static __device__ __forceinline__ T det2(T m0, T m1, T m2, T m3) { return t_fma(m0, m3, -(m1 * m2)); }
+    __device__ __forceinline__ T pre(const P& r, const P& c, T& s, Pieces& e) const {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e.a[k] = T(0.5) * (r.s[k] + c.s[k]);
+        e.b0 = e.a[0] + this->jit; e.b3 = e.a[3] + this->jit;
+        e.iB = t_rcp(det2(e.b0, e.a[1], e.a[2], e.b3));
+        e.d0 = r.x[0] - c.x[0]; e.d1 = r.x[1] - c.x[1];
+        const T s2 = T(2) * (e.b3 * e.d0 * e.d0 - (e.a[1] + e.a[2]) * e.d0 * e.d1 + e.b0 * e.d1 * e.d1) * e.iB;
+        e.neg = s2 < T(0);
+        s = e.neg ? T(0) : s2;
+        e.detA = det2(e.a[0], e.a[1], e.a[2], e.a[3]);
+        return r.q * c.q * t_rsqrt(e.detA);
+    }
+    __device__ __forceinline__ T eval(int64_t, const P& r, const P& c) const {
+        T s;
+        Pieces e;
+        const T p = pre(r, c, s, e);
+        return p * Radial::eval(s);
+    }
+    __device__ __forceinline__ T feval(int64_t b, const P& r, const P& c) const { return eval(b, r, c); }
+    // 1 / (4 det) of det A, det S1 and det S2: ONE spelling (see prod_diff).  float: v_rcp_f32, one instruction; double: from
+    // rsqrt(det), since a float64 division costs twice t_rsqrt.  det < 0 has no prefactor (NaN) either way.
+    static __device__ __forceinline__ T quarter_inv(T det) {
+        if constexpr (sizeof(T) == 4) return T(0.25) * t_rcp(det);
+        const T rs = t_rsqrt(det);
+        return T(0.25) * rs * rs;
+    }
+    // m n - p q with both products rounded, never fused: exactly 0 for (m, n) == (p, q), so that an entry with delta = 0
+    // and S1 == S2 bit for bit (the diagonal of K(x, x)) adds exactly nothing to the gradient
+    static __device__ __forceinline__ T prod_diff(T m, T n, T p, T q) {
+#pragma clang fp contract(off)
+        const T mn = m * n, pq = p * q;
+        return mn - pq;
+    }
+    __device__ __forceinline__ void grad(int64_t, const P& r, const P& c, T g, T* ra, T* ca, T*) const {
+        T s, q;
+        Pieces e;
+        const T p = pre(r, c, s, e);
+        const T kap = Radial::eval(s, &q);
+        const T w = g * p;
+        const T wk = w * kap;
+        const T h = e.neg ? T(0) : T(-0.5) * w * q;                                  // -1/2 g P phi
+        const T v0 = (e.b3 * e.d0 - e.a[1] * e.d1) * e.iB, v1 = (e.b0 * e.d1 - e.a[2] * e.d0) * e.iB;      // B^-1 delta
+        const T u0 = (e.b3 * e.d0 - e.a[2] * e.d1) * e.iB, u1 = (e.b0 * e.d1 - e.a[1] * e.d0) * e.iB;      // B^-T delta
+        const T hu0 = h * u0, hu1 = h * u1;
+        const T t0 = hu0 * v0, t1 = hu0 * v1, t2 = hu1 * v0, t3 = hu1 * v1;
+        const T iA = quarter_inv(e.detA);
+        const T dr = quarter_inv(det2(r.s[0], r.s[1], r.s[2], r.s[3]));
+        const T dc = quarter_inv(det2(c.s[0], c.s[1], c.s[2], c.s[3]));
+        ra[0] += wk * prod_diff(dr, r.s[3], iA, e.a[3]) + t0; ra[1] += wk * prod_diff(iA, e.a[2], dr, r.s[2]) + t1;
+        ra[2] += wk * prod_diff(iA, e.a[1], dr, r.s[1]) + t2; ra[3] += wk * prod_diff(dr, r.s[0], iA, e.a[0]) + t3;
+        ca[0] += wk * prod_diff(dc, c.s[3], iA, e.a[3]) + t0; ca[1] += wk * prod_diff(iA, e.a[2], dc, c.s[2]) + t1;
+        ca[2] += wk * prod_diff(iA, e.a[1], dc, c.s[1]) + t2; ca[3] += wk * prod_diff(dc, c.s[0], iA, e.a[0]) + t3;
     }
 };
 
@@ -852,19 +925,50 @@ int ps_fwd(const T* x1, const T* x2, const T* s1, const T* s2, int64_t n1, int64
     return launch_fwd<T>(op, 1, n1, n2, T(0), (const T*)nullptr, K, ldk, 0, stream);
 }
 
-template <typename T>
-int ps_bwd(const T* x1, const T* x2, const T* s1, const T* s2, int64_t n1, int64_t n2, T jit, const T* G,
-           int64_t ldg, T* g_s1, T* g_s2, void* ws, size_t wsb, void* stream) {
-    if (!x1) return -1; if (!x2) return -2; if (!s1) return -3; if (!s2) return -4;
-    if (n1 < 0) return -5; if (n2 < 0) return -6; if (!G && n1 * n2 > 0) return -8; if (ldg < n2) return -9;
-    using Op = PsOp<T>;
-    Op op{x1, x2, s1, s2, jit};
+// The backward launch of the Paciorek-Schervish family (PsOp, PsRadialOp): one accumulator layout, so one output wiring.
+template <typename T, typename Op>
+int ps_launch_bwd(const Op& op, int64_t n1, int64_t n2, const T* G, int64_t ldg, T* g_s1, T* g_s2, void* ws, size_t wsb,
+                  void* stream) {
     OutDesc<T> rows = empty_desc<T>(4), cols = empty_desc<T>(4), globs = empty_desc<T>(0);
     for (int k = 0; k < 4; ++k) {
         if (g_s1) { rows.ptr[k] = g_s1 + k; rows.stride[k] = 4; }
         if (g_s2) { cols.ptr[k] = g_s2 + k; cols.stride[k] = 4; }
     }
     return launch_bwd<T>(op, 1, n1, n2, G, ldg, 0, rows, cols, globs, ws, wsb, stream);
+}
+
+template <typename T>
+int ps_bwd(const T* x1, const T* x2, const T* s1, const T* s2, int64_t n1, int64_t n2, T jit, const T* G,
+           int64_t ldg, T* g_s1, T* g_s2, void* ws, size_t wsb, void* stream) {
+    if (!x1) return -1; if (!x2) return -2; if (!s1) return -3; if (!s2) return -4;
+    if (n1 < 0) return -5; if (n2 < 0) return -6; if (!G && n1 * n2 > 0) return -8; if (ldg < n2) return -9;
+    PsOp<T> op{x1, x2, s1, s2, jit};
+    return ps_launch_bwd<T>(op, n1, n2, G, ldg, g_s1, g_s2, ws, wsb, stream);
+}
+
+// K3': the Paciorek-Schervish signatures with nu2 after n2 (so every later argument's index is one up)
+template <typename T>
+int ps_matern_fwd(const T* x1, const T* x2, const T* s1, const T* s2, int64_t n1, int64_t n2, int nu2, T jit, T* K,
+                  int64_t ldk, void* stream) {
+    if (!x1) return -1; if (!x2) return -2; if (!s1) return -3; if (!s2) return -4;
+    if (n1 < 0) return -5; if (n2 < 0) return -6; if (!matern_nu2_ok(nu2)) return -7;
+    if (!K && n1 * n2 > 0) return -9; if (ldk < n2) return -10;
+    return dispatch_nu2(nu2, [&](auto radial) {
+        PsRadialOp<T, decltype(radial)> op{{x1, x2, s1, s2, jit}};
+        return launch_fwd<T>(op, 1, n1, n2, T(0), (const T*)nullptr, K, ldk, 0, stream);
+    });
+}
+
+template <typename T>
+int ps_matern_bwd(const T* x1, const T* x2, const T* s1, const T* s2, int64_t n1, int64_t n2, int nu2, T jit,
+                  const T* G, int64_t ldg, T* g_s1, T* g_s2, void* ws, size_t wsb, void* stream) {
+    if (!x1) return -1; if (!x2) return -2; if (!s1) return -3; if (!s2) return -4;
+    if (n1 < 0) return -5; if (n2 < 0) return -6; if (!matern_nu2_ok(nu2)) return -7;
+    if (!G && n1 * n2 > 0) return -9; if (ldg < n2) return -10;
+    return dispatch_nu2(nu2, [&](auto radial) {
+        PsRadialOp<T, decltype(radial)> op{{x1, x2, s1, s2, jit}};
+        return ps_launch_bwd<T>(op, n1, n2, G, ldg, g_s1, g_s2, ws, wsb, stream);
+    });
 }
 
 template <typename T>
@@ -1046,6 +1150,24 @@ int nsgp_ps2d_build_bwd_f64(const double* x1, const double* x2, const double* s1
     return ps_bwd<double>(x1, x2, s1, s2, n1, n2, jit, G, ldg, g_s1, g_s2, ws, wsb, stream);
 }
 
+int nsgp_ps2d_matern_build_fwd_f32(const float* x1, const float* x2, const float* s1, const float* s2, int64_t n1,
+                                   int64_t n2, int nu2, float jit, float* K, int64_t ldk, void* stream) {
+    return ps_matern_fwd<float>(x1, x2, s1, s2, n1, n2, nu2, jit, K, ldk, stream);
+}
+int nsgp_ps2d_matern_build_fwd_f64(const double* x1, const double* x2, const double* s1, const double* s2, int64_t n1,
+                                   int64_t n2, int nu2, double jit, double* K, int64_t ldk, void* stream) {
+    return ps_matern_fwd<double>(x1, x2, s1, s2, n1, n2, nu2, jit, K, ldk, stream);
+}
+int nsgp_ps2d_matern_build_bwd_f32(const float* x1, const float* x2, const float* s1, const float* s2, int64_t n1,
+                                   int64_t n2, int nu2, float jit, const float* G, int64_t ldg, float* g_s1,
+                                   float* g_s2, void* ws, size_t wsb, void* stream) {
+    return ps_matern_bwd<float>(x1, x2, s1, s2, n1, n2, nu2, jit, G, ldg, g_s1, g_s2, ws, wsb, stream);
+}
+int nsgp_ps2d_matern_build_bwd_f64(const double* x1, const double* x2, const double* s1, const double* s2, int64_t n1,
+                                   int64_t n2, int nu2, double jit, const double* G, int64_t ldg, double* g_s1,
+                                   double* g_s2, void* ws, size_t wsb, void* stream) {
+    return ps_matern_bwd<double>(x1, x2, s1, s2, n1, n2, nu2, jit, G, ldg, g_s1, g_s2, ws, wsb, stream);
+}
 
 int nsgp_rbf_periodic_build_fwd_f32(const float* x1, const float* x2, const float* ls_rbf, const float* ls_per,
                                     const float* period, const float* os, int64_t batch, int64_t n1, int64_t n2, int D,

@@ -1,13 +1,17 @@
 """Paciorek-Schervish ("multivariate Gibbs") kernel with a matrix-normal prior on the latent H, on
 the MI355X engine -- drop-in for models/multivariate_gibbs_kernel.py of the reference.
 
-  MultivariateGibbsKernel(x, input_dim)  with .H (N,2), .D (2,2),
+  MultivariateGibbsKernel(x, input_dim, *, nu=None)  with .H (N,2), .D (2,2),
       .expectation_conditional_matrix_variate_dist(x_star), .forward(x1, x2, diag=False)   ref :20-150
   Sigma_i = softplus((h_i h_i^T)**2) + D**2 (elementwise squares);  H enters DETACHED (ref :85,98), so
   K has gradients w.r.t. D only.  The reference's Python loop over N through numpy and its
   (N,N,2,2) det / inverse temporaries are one gfx950 launch with closed-form 2x2 algebra
   (nsgp_ps2d_build_fwd).  The conditional mean kron(col, R*) kron(col^-1, R^-1) vec(H) is evaluated
   as R* R^-1 H (identical by the mixed-product rule; no (2N*) x (2N) Kronecker matrix).
+nu = None is the reference's squared-exponential kernel; nu in {0.5, 1.5, 2.5} is the Matern form Paciorek & Schervish
+(2006) give for a full Sigma(x), k = P * Matern_nu(sqrt(2 Q)) with the same prefactor P and quadratic form Q
+(nsgp_ps2d_matern_build_fwd): nu is the roughness of the field, not of Sigma(x), so the row kernel of the prior on H and
+the conditional mean stay RBF.
 Quirks kept (SURVEY Appendix B / DESIGN.md): `lengthscale=` passed to RBFKernel is swallowed by
 gpytorch's Kernel.__init__(**kwargs), so the row kernel really has lengthscale softplus(0); the
 cross-covariance branch decides which side carries H by comparing lengths.  The reference's
@@ -33,8 +37,11 @@ def _sigma(H, D):
 class MultivariateGibbsKernel(gpytorch.kernels.Kernel):
     is_stationary = False
 
-    def __init__(self, x, input_dim, **kwargs):
+    def __init__(self, x, input_dim, *, nu=None, **kwargs):
+        if nu is not None and nu not in {0.5, 1.5, 2.5}:
+            raise RuntimeError('nu expected to be 0.5, 1.5, or 2.5')
         super().__init__(**kwargs)
+        self.nu = nu
         self.x = x
         self.n = len(x)
         self.d = input_dim
@@ -83,5 +90,5 @@ class MultivariateGibbsKernel(gpytorch.kernels.Kernel):
         s1 = _sigma(H1, self.D)
         s2 = s1 if H2 is H1 else _sigma(H2, self.D)
         self.sigma_matrix_i, self.sigma_matrix_j = s1, s2
-        K = ops.ps2d_kernel(x1, x2, s1, s2, jitter)
+        K = ops.ps2d_kernel(x1, x2, s1, s2, jitter, nu=self.nu)
         return torch.diagonal(K, dim1=-1, dim2=-2) if diag else K

@@ -2,12 +2,13 @@
 models/sparse_multivariate_gibbs_kernel.py of the reference (:20-154), whose broken import
 `kernels.latent_priors` (:11) is fixed to models.latent_priors.
 
-  SparseMultivariateGibbsKernel(Z, input_dim, Z_init)  with .H (M,2), .D (2,2),
+  SparseMultivariateGibbsKernel(Z, input_dim, Z_init, *, nu=None)  with .H (M,2), .D (2,2),
       .expectation_conditional_matrix_variate_dist(x_star), .forward(x1, x2, diag=False)
 Differences from the dense variant, as in the reference: row kernel ScaleKernel(RBF) (the
 `lengthscale=[1.3, 1.1]` keyword is swallowed by gpytorch's Kernel.__init__),
 column covariance I, the PRIOR uses the static row covariance of Z_init while the conditional mean
 re-inverts the row covariance of the CURRENT Z at every call (:69).
+nu as in MultivariateGibbsKernel: None, or 0.5 / 1.5 / 2.5 for the Matern form of the kernel (not of the row kernel).
 """
 import torch
 
@@ -23,8 +24,11 @@ jitter = 1e-5
 class SparseMultivariateGibbsKernel(gpytorch.kernels.Kernel):
     is_stationary = False
 
-    def __init__(self, Z, input_dim, Z_init, **kwargs):
+    def __init__(self, Z, input_dim, Z_init, *, nu=None, **kwargs):
+        if nu is not None and nu not in {0.5, 1.5, 2.5}:
+            raise RuntimeError('nu expected to be 0.5, 1.5, or 2.5')
         super().__init__(**kwargs)
+        self.nu = nu
         self.inducing_locations = Z
         self.d = input_dim
         self.m = self.inducing_locations.shape[0]
@@ -70,5 +74,5 @@ class SparseMultivariateGibbsKernel(gpytorch.kernels.Kernel):
         s1 = _sigma(H1, self.D)
         s2 = s1 if H2 is H1 else _sigma(H2, self.D)
         self.sigma_matrix_i, self.sigma_matrix_j = s1, s2
-        K = ops.ps2d_kernel(x1, x2, s1, s2, jitter)
+        K = ops.ps2d_kernel(x1, x2, s1, s2, jitter, nu=self.nu)
         return torch.diagonal(K, dim1=-1, dim2=-2) if diag else K

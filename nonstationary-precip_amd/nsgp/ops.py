@@ -386,24 +386,39 @@ def _ps_args(x1, x2, s1, s2):
     return ref, n1, n2
 
 
-def ps2d_build(x1, x2, s1, s2, jitter=1e-5):
+def _ps_entry(nu):
+    """(library stem, the scalars its entry points take after n2) of the Paciorek-Schervish build: nu = None is the
+    squared-exponential kernel, nu in {0.5, 1.5, 2.5} its Matern form (K3', nu2 = 2 nu).  Any other value raises as
+    _gibbs_entry."""
+    if nu is None:
+        return 'ps2d', ()
+    if nu not in MATERN_NU:
+        raise RuntimeError('nu expected to be 0.5, 1.5, or 2.5')
+    return 'ps2d_matern', (int(2 * nu),)
+
+
+def ps2d_build(x1, x2, s1, s2, jitter=1e-5, nu=None):
+    """K = |S1|^(1/4) |S2|^(1/4) |A|^(-1/2) exp(-Q), A = (S1 + S2) / 2, Q = d^T (A + jitter I)^-1 d.
+    nu in {0.5, 1.5, 2.5}: Matern_nu(sqrt(2 Q)) in place of exp(-Q) (include/nsgp.h, K3')."""
+    stem, extra = _ps_entry(nu)
     ref, n1, n2 = _ps_args(x1, x2, s1, s2)
     x1, x2, s1, s2 = _c(x1), _c(x2), _c(s1), _c(s2)
     K = torch.empty((n1, n2), dtype=ref.dtype, device=ref.device)
-    _lib.call(f'nsgp_ps2d_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(s1), _p(s2), n1, n2, float(jitter), _p(K), n2,
-              _stream())
+    _lib.call(f'nsgp_{stem}_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(s1), _p(s2), n1, n2, *extra, float(jitter), _p(K),
+              n2, _stream())
     return K
 
 
-def ps2d_build_bwd(x1, x2, s1, s2, jitter, G):
+def ps2d_build_bwd(x1, x2, s1, s2, jitter, G, nu=None):
+    stem, extra = _ps_entry(nu)
     ref, n1, n2 = _ps_args(x1, x2, s1, s2)
     _chk(ref, G)
     x1, x2, s1, s2, G = _c(x1), _c(x2), _c(s1), _c(s2), _c(G)
     g1, g2 = torch.empty_like(s1), torch.empty_like(s2)
     lib = _lib.load()
     ws = _ws(lib.nsgp_ps2d_build_bwd_workspace(n1, n2, ref.element_size()), ref.device)
-    _lib.call(f'nsgp_ps2d_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(s1), _p(s2), n1, n2, float(jitter), _p(G), n2,
-              _p(g1), _p(g2), _p(ws), ws.numel(), _stream())
+    _lib.call(f'nsgp_{stem}_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(s1), _p(s2), n1, n2, *extra, float(jitter), _p(G),
+              n2, _p(g1), _p(g2), _p(ws), ws.numel(), _stream())
     return g1, g2
 
 
@@ -1484,20 +1499,23 @@ class RbfPeriodicKernelFn(torch.autograd.Function):
 
 
 class Ps2dKernelFn(torch.autograd.Function):
-    """Paciorek-Schervish kernel for per-point 2x2 matrices (models/multivariate_gibbs_kernel.py:98-150)."""
+    """Paciorek-Schervish kernel for per-point 2x2 matrices (models/multivariate_gibbs_kernel.py:98-150).
+    nu = None: the squared-exponential kernel; 0.5, 1.5, 2.5: its Matern form.  x1 and x2 get no gradient."""
 
     @staticmethod
-    def forward(ctx, x1, x2, s1, s2, jitter):
+    def forward(ctx, x1, x2, s1, s2, jitter, nu=None):
         ctx.save_for_backward(x1, x2, s1, s2)
         ctx.jitter = jitter
-        return ps2d_build(x1, x2, s1, s2, jitter)
+        ctx.nu = nu
+        return ps2d_build(x1, x2, s1, s2, jitter, nu=nu)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
         x1, x2, s1, s2 = ctx.saved_tensors
-        g1, g2 = ps2d_build_bwd(x1, x2, s1, s2, ctx.jitter, G)
-        return None, None, g1 if ctx.needs_input_grad[2] else None, g2 if ctx.needs_input_grad[3] else None, None
+        g1, g2 = ps2d_build_bwd(x1, x2, s1, s2, ctx.jitter, G, nu=ctx.nu)
+        return (None, None, g1 if ctx.needs_input_grad[2] else None, g2 if ctx.needs_input_grad[3] else None, None,
+                None)
 
 
 def _tri_flags(ta, tb, a_lower, b_lower, out_lower):
@@ -1601,8 +1619,8 @@ def rbf_periodic_kernel(x1, x2, ls_rbf, ls_per, period, os_=None, diag_add=0.0):
     return RbfPeriodicKernelFn.apply(x1, x2, ls_rbf, ls_per, period, os_, diag_add)
 
 
-def ps2d_kernel(x1, x2, s1, s2, jitter=1e-5):
-    return Ps2dKernelFn.apply(x1, x2, s1, s2, jitter)
+def ps2d_kernel(x1, x2, s1, s2, jitter=1e-5, nu=None):
+    return Ps2dKernelFn.apply(x1, x2, s1, s2, jitter, nu)
 
 
 class GaussEllFn(torch.autograd.Function):
