@@ -321,6 +321,37 @@ int nsgp_rbf_periodic_build_bwd_f64(const double* x1, const double* x2, const do
                                     double* g_os, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K2''' Batched  os * Matern_nu-ARD(x; ls_env) * Periodic(x; ls_per, period)  in one launch:
+ *       k = os_b kappa_nu(s) exp(-2 sin^2(pi |x - x'| / period_b) / ls_per_b),  s = sum_d ((x_d - x'_d)/ls_env[b,d])^2
+ *     replaces ScaleKernel(MaternKernel(nu, active_dims=0) * PeriodicKernel(active_dims=0)): the temporal kernel
+ *     nsgp_rbf_periodic_build_* with a Matern envelope.  kappa_nu is the radial function of nsgp_matern_build_*
+ *     (nu2 = 2 nu in {1, 3, 5}; nu = 1/2 takes the derivative at zero distance as 0); the periodic factor is that of
+ *     nsgp_rbf_periodic_build_*.  The signatures are the rbf_periodic ones with ls_rbf named ls_env and `int nu2` after
+ *     sx2; ls_env == NULL is an error here (the plain PeriodicKernel stays with rbf_periodic); os == NULL means 1.
+ *     backward: outputs as rbf_periodic; the workspace is the same too (same accumulator layout): size it with
+ *     nsgp_rbf_periodic_build_bwd_workspace, there is no second query.  g_x1 == g_x2 sums both sides into one buffer.
+ *     A bad argument returns the negative 1-based index in these signatures (nu2: -13).
+ * ------------------------------------------------------------------------------------------ */
+int nsgp_matern_periodic_build_fwd_f32(const float* x1, const float* x2, const float* ls_env, const float* ls_per,
+                                       const float* period, const float* os, int64_t batch, int64_t n1, int64_t n2,
+                                       int D, int64_t sx1, int64_t sx2, int nu2, float diag_add, float* K, int64_t ldk,
+                                       int64_t sK, void* stream);
+int nsgp_matern_periodic_build_fwd_f64(const double* x1, const double* x2, const double* ls_env, const double* ls_per,
+                                       const double* period, const double* os, int64_t batch, int64_t n1, int64_t n2,
+                                       int D, int64_t sx1, int64_t sx2, int nu2, double diag_add, double* K,
+                                       int64_t ldk, int64_t sK, void* stream);
+int nsgp_matern_periodic_build_bwd_f32(const float* x1, const float* x2, const float* ls_env, const float* ls_per,
+                                       const float* period, const float* os, int64_t batch, int64_t n1, int64_t n2,
+                                       int D, int64_t sx1, int64_t sx2, int nu2, const float* G, int64_t ldg,
+                                       int64_t sG, float* g_x1, float* g_x2, float* g_ls_env, float* g_ls_per,
+                                       float* g_period, float* g_os, void* ws, size_t ws_bytes, void* stream);
+int nsgp_matern_periodic_build_bwd_f64(const double* x1, const double* x2, const double* ls_env, const double* ls_per,
+                                       const double* period, const double* os, int64_t batch, int64_t n1, int64_t n2,
+                                       int D, int64_t sx1, int64_t sx2, int nu2, const double* G, int64_t ldg,
+                                       int64_t sG, double* g_x1, double* g_x2, double* g_ls_env, double* g_ls_per,
+                                       double* g_period, double* g_os, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K4  Blocked right-looking Cholesky A = L L^T (lower, in place, strict upper zeroed), batched.
  *     Panel: LDS-resident 64x64 diagonal factor + explicit inverse; trailing update on MFMA.
  *     replaces psd_safe_cholesky (models/gibbs_kernels.py:201,298), gpytorch

@@ -318,6 +318,82 @@ template <typename T, int D> struct RbfPeriodicOp {
     }
 };
 
+// K2''' batched  os * kappa(s) * Periodic(x; ls_p, period),  s = sum_d (delta_d / ls_e,d)^2:  the temporal kernel with a
+// radial envelope from radial.h in place of the squared exponential,
+//   k = os kappa(s) E,   E = exp(-2 sin^2(theta) / ls_p),   theta = pi |delta| / period.
+// A sibling of RbfPeriodicOp as GibbsRadialOp is of GibbsOp: the members, the per-point operands (P, point, row, col,
+// fcol) and the accumulator layout (NR / NC / NG: ls_e[D], ls_p, period, os) are inherited, so the launchers, the OutDesc
+// wiring (rbfper_launch_bwd), the workspace size and the one-buffer symmetric mode are RbfPeriodicOp's, and
+// RbfPeriodicOp's own code is not touched.  `lsr` is the envelope lengthscale and is required (the entry points check).
+// E is RbfPeriodicOp's spelling (library sin / cos / exp, division by ls_p); kappa, its range, far tail (0 * E with
+// E <= 1, never inf * 0), NaN behaviour and phi(0) = 0 for nu = 1/2 are the policy's.  The two sums are explicit fmas:
+// forward and backward see one s and one r per entry, whatever -ffp-contract makes of the neighbouring code.
+// With phi = (d kappa / d d) / d as the policy returns it, u_d = delta_d / ls_e,d and c = (4 / ls_p) sin cos pi:
+//   dk/dx1_d = os E phi u_d / ls_e,d - k (c / period) delta_d / r = -dk/dx2_d        (second term 0 at r = 0)
+//   dk/dls_e,d = -os E phi u_d^2 / ls_e,d    dk/dls_p = k 2 sin^2 / ls_p^2    dk/dperiod = k c r / period^2    dk/dos = kappa E
+// An entry with delta = 0 (the diagonal of K(x, x)) has u = 0, r = 0 and sin = 0: every term but dk/dos is exactly 0.
+template <typename T, int D, typename Radial> struct RadialPeriodicOp : RbfPeriodicOp<T, D> {
+    using B = RbfPeriodicOp<T, D>;
+    using P = typename B::P;
+    static constexpr int DM = B::DM;
+    // the periodic factor E (returned) and the pieces of one entry: s, r = |delta|, (sn, cs) = sincos(theta)
+    __device__ __forceinline__ T base(int64_t b, const P& r, const P& c, T& s, T& rr, T& sn, T& cs) const {
+        T q = T(0), r2 = T(0);
+#pragma unroll
+        for (int d = 0; d < DM; ++d) {
+            if (D || d < this->Drt) {
+                const T df = r.x[d] - c.x[d];
+                const T u = df * (T(1) / this->lsr[b * this->Drt + d]);
+                r2 = t_fma(df, df, r2);
+                q = t_fma(u, u, q);
+            }
+        }
+        s = q;
+        rr = t_sqrt(r2);
+        const T th = T(3.14159265358979323846) * rr / this->per[b];
+        sn = sin(th); cs = cos(th);
+        return t_exp(T(-2) * sn * sn / this->lsp[b]);
+    }
+    __device__ __forceinline__ T eval(int64_t b, const P& r, const P& c) const {
+        T s, rr, sn, cs;
+        const T e = base(b, r, c, s, rr, sn, cs);
+        const T k = Radial::eval(s) * e;
+        return this->os ? this->os[b] * k : k;
+    }
+    __device__ __forceinline__ T feval(int64_t b, const P& r, const P& c) const { return eval(b, r, c); }
+    __device__ __forceinline__ void grad(int64_t b, const P& r, const P& c, T g, T* ra, T* ca, T* ga) const {
+        T s, rr, sn, cs, q;
+        const T e = base(b, r, c, s, rr, sn, cs);
+        const T kap = Radial::eval(s, &q);
+        ga[DM + 2] += g * (kap * e);                                       // d/d os
+        const T we = g * e * (this->os ? this->os[b] : T(1));
+        const T w = we * kap, wq = we * q;                                 // g k;  g os E phi (-phi for a negated policy)
+        const T ilp = T(1) / this->lsp[b], ip = T(1) / this->per[b];
+        ga[DM] += w * T(2) * sn * sn * ilp * ilp;                          // d/d ls_p
+        const T dsdu = T(4) * ilp * sn * cs * T(3.14159265358979323846);   // c: -(d log E / d theta)
+        ga[DM + 1] += w * dsdu * rr * ip * ip;                             // d/d period  (d theta / dp = -pi r / p^2)
+        const T wr = rr > T(0) ? w * dsdu * ip / rr : T(0);                // g k (c / period) / r
+#pragma unroll
+        for (int d = 0; d < DM; ++d) {
+            if (D || d < this->Drt) {
+                const T df = r.x[d] - c.x[d];
+                const T il = T(1) / this->lsr[b * this->Drt + d];
+                const T u = df * il;
+                const T gu = wq * u * il;                                  // g os E (+-phi) u_d / ls_e,d
+                if constexpr (Radial::negated) {
+                    const T gx = -gu - wr * df;
+                    ra[d] += gx; ca[d] -= gx;
+                    ga[d] += gu * u;                                       // d/d ls_e,d
+                } else {
+                    const T gx = gu - wr * df;
+                    ra[d] += gx; ca[d] -= gx;
+                    ga[d] -= gu * u;
+                }
+            }
+        }
+    }
+};
+
 template <typename T> struct PsOp {
     static constexpr int NR = 4, NC = 4, NG = 1;      // NG unused (kept 1 for array sizing)
     const T *x1, *x2, *s1, *s2;
@@ -983,6 +1059,25 @@ int rbfper_fwd(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* pe
         return launch_fwd<T>(op, batch, n1, n2, diag_add, (const T*)nullptr, K, ldk, sK, stream);
     });
 }
+// The backward launch of the periodic family (RbfPeriodicOp, RadialPeriodicOp): one accumulator layout, so one output wiring.
+template <typename T, typename Op>
+int rbfper_launch_bwd(const Op& op, int64_t batch, const T* G, int64_t ldg, int64_t sG, T* g_x1, T* g_x2, T* g_lsr,
+                      T* g_lsp, T* g_per, T* g_os, void* ws, size_t wsb, void* stream) {
+    constexpr int DM = Op::DM;
+    const int D = op.Drt;
+    const int64_t n1 = op.n1, n2 = op.n2;
+    OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
+    for (int d = 0; d < D; ++d) {
+        if (g_x1) { rows.ptr[d] = g_x1 + d; rows.stride[d] = D; rows.bstride[d] = n1 * D; }
+        if (g_x2) { cols.ptr[d] = g_x2 + d; cols.stride[d] = D; cols.bstride[d] = n2 * D; }
+        if (g_lsr && op.lsr) { globs.ptr[d] = g_lsr + d; globs.bstride[d] = D; }
+    }
+    if (g_lsp) { globs.ptr[DM] = g_lsp; globs.bstride[DM] = 1; }
+    if (g_per) { globs.ptr[DM + 1] = g_per; globs.bstride[DM + 1] = 1; }
+    if (g_os) { globs.ptr[DM + 2] = g_os; globs.bstride[DM + 2] = 1; }
+    return launch_bwd<T>(op, batch, n1, n2, G, ldg, sG, rows, cols, globs, ws, wsb, stream);
+}
+
 template <typename T>
 int rbfper_bwd(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* per, const T* os, int64_t batch,
                int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, const T* G, int64_t ldg, int64_t sG, T* g_x1,
@@ -991,19 +1086,45 @@ int rbfper_bwd(const T* x1, const T* x2, const T* lsr, const T* lsp, const T* pe
     if (batch < 0) return -7; if (n1 < 0) return -8; if (n2 < 0) return -9; if (D < 1 || D > NSGP_MAX_DIM) return -10;
     if (!G && batch * n1 * n2 > 0) return -13; if (ldg < n2) return -14;
     return dispatch_dim<1, 2>(D, [&](auto dim) {
-        using Op = RbfPeriodicOp<T, decltype(dim)::value>;
-        Op op{x1, x2, lsr, lsp, per, os, n1, n2, sx1, sx2, D};
-        constexpr int DM = Op::DM;
-        OutDesc<T> rows = empty_desc<T>(Op::NR), cols = empty_desc<T>(Op::NC), globs = empty_desc<T>(Op::NG);
-        for (int d = 0; d < D; ++d) {
-            if (g_x1) { rows.ptr[d] = g_x1 + d; rows.stride[d] = D; rows.bstride[d] = n1 * D; }
-            if (g_x2) { cols.ptr[d] = g_x2 + d; cols.stride[d] = D; cols.bstride[d] = n2 * D; }
-            if (g_lsr && lsr) { globs.ptr[d] = g_lsr + d; globs.bstride[d] = D; }
-        }
-        if (g_lsp) { globs.ptr[DM] = g_lsp; globs.bstride[DM] = 1; }
-        if (g_per) { globs.ptr[DM + 1] = g_per; globs.bstride[DM + 1] = 1; }
-        if (g_os) { globs.ptr[DM + 2] = g_os; globs.bstride[DM + 2] = 1; }
-        return launch_bwd<T>(op, batch, n1, n2, G, ldg, sG, rows, cols, globs, ws, wsb, stream);
+        RbfPeriodicOp<T, decltype(dim)::value> op{x1, x2, lsr, lsp, per, os, n1, n2, sx1, sx2, D};
+        return rbfper_launch_bwd<T>(op, batch, G, ldg, sG, g_x1, g_x2, g_lsr, g_lsp, g_per, g_os, ws, wsb, stream);
+    });
+}
+
+// K2''': the rbf_periodic signatures with the envelope lengthscale required and nu2 after sx2 (so every later argument's
+// index is one up)
+template <typename T>
+int matper_check(const T* x1, const T* x2, const T* lse, const T* lsp, const T* per, int64_t batch, int64_t n1,
+                 int64_t n2, int D, int nu2) {
+    if (!x1) return -1; if (!x2) return -2; if (!lse) return -3; if (!lsp) return -4; if (!per) return -5;
+    if (batch < 0) return -7; if (n1 < 0) return -8; if (n2 < 0) return -9; if (D < 1 || D > NSGP_MAX_DIM) return -10;
+    if (!matern_nu2_ok(nu2)) return -13;
+    return 0;
+}
+template <typename T>
+int matper_fwd(const T* x1, const T* x2, const T* lse, const T* lsp, const T* per, const T* os, int64_t batch,
+               int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2, T diag_add, T* K, int64_t ldk,
+               int64_t sK, void* stream) {
+    if (const int bad = matper_check(x1, x2, lse, lsp, per, batch, n1, n2, D, nu2)) return bad;
+    if (!K && batch * n1 * n2 > 0) return -15; if (ldk < n2) return -16;
+    return dispatch_nu2(nu2, [&](auto radial) {
+        return dispatch_dim<1, 2>(D, [&](auto d) {
+            RadialPeriodicOp<T, decltype(d)::value, decltype(radial)> op{{x1, x2, lse, lsp, per, os, n1, n2, sx1, sx2, D}};
+            return launch_fwd<T>(op, batch, n1, n2, diag_add, (const T*)nullptr, K, ldk, sK, stream);
+        });
+    });
+}
+template <typename T>
+int matper_bwd(const T* x1, const T* x2, const T* lse, const T* lsp, const T* per, const T* os, int64_t batch,
+               int64_t n1, int64_t n2, int D, int64_t sx1, int64_t sx2, int nu2, const T* G, int64_t ldg, int64_t sG,
+               T* g_x1, T* g_x2, T* g_lse, T* g_lsp, T* g_per, T* g_os, void* ws, size_t wsb, void* stream) {
+    if (const int bad = matper_check(x1, x2, lse, lsp, per, batch, n1, n2, D, nu2)) return bad;
+    if (!G && batch * n1 * n2 > 0) return -14; if (ldg < n2) return -15;
+    return dispatch_nu2(nu2, [&](auto radial) {
+        return dispatch_dim<1, 2>(D, [&](auto dim) {
+            RadialPeriodicOp<T, decltype(dim)::value, decltype(radial)> op{{x1, x2, lse, lsp, per, os, n1, n2, sx1, sx2, D}};
+            return rbfper_launch_bwd<T>(op, batch, G, ldg, sG, g_x1, g_x2, g_lse, g_lsp, g_per, g_os, ws, wsb, stream);
+        });
     });
 }
 
@@ -1200,6 +1321,37 @@ int nsgp_rbf_periodic_build_bwd_f64(const double* x1, const double* x2, const do
                                     double* g_os, void* ws, size_t wsb, void* stream) {
     return rbfper_bwd<double>(x1, x2, ls_rbf, ls_per, period, os, batch, n1, n2, D, sx1, sx2, G, ldg, sG, g_x1, g_x2,
                               g_ls_rbf, g_ls_per, g_period, g_os, ws, wsb, stream);
+}
+
+int nsgp_matern_periodic_build_fwd_f32(const float* x1, const float* x2, const float* ls_env, const float* ls_per,
+                                       const float* period, const float* os, int64_t batch, int64_t n1, int64_t n2,
+                                       int D, int64_t sx1, int64_t sx2, int nu2, float diag_add, float* K, int64_t ldk,
+                                       int64_t sK, void* stream) {
+    return matper_fwd<float>(x1, x2, ls_env, ls_per, period, os, batch, n1, n2, D, sx1, sx2, nu2, diag_add, K, ldk, sK,
+                             stream);
+}
+int nsgp_matern_periodic_build_fwd_f64(const double* x1, const double* x2, const double* ls_env, const double* ls_per,
+                                       const double* period, const double* os, int64_t batch, int64_t n1, int64_t n2,
+                                       int D, int64_t sx1, int64_t sx2, int nu2, double diag_add, double* K,
+                                       int64_t ldk, int64_t sK, void* stream) {
+    return matper_fwd<double>(x1, x2, ls_env, ls_per, period, os, batch, n1, n2, D, sx1, sx2, nu2, diag_add, K, ldk, sK,
+                              stream);
+}
+int nsgp_matern_periodic_build_bwd_f32(const float* x1, const float* x2, const float* ls_env, const float* ls_per,
+                                       const float* period, const float* os, int64_t batch, int64_t n1, int64_t n2,
+                                       int D, int64_t sx1, int64_t sx2, int nu2, const float* G, int64_t ldg,
+                                       int64_t sG, float* g_x1, float* g_x2, float* g_ls_env, float* g_ls_per,
+                                       float* g_period, float* g_os, void* ws, size_t wsb, void* stream) {
+    return matper_bwd<float>(x1, x2, ls_env, ls_per, period, os, batch, n1, n2, D, sx1, sx2, nu2, G, ldg, sG, g_x1, g_x2,
+                             g_ls_env, g_ls_per, g_period, g_os, ws, wsb, stream);
+}
+int nsgp_matern_periodic_build_bwd_f64(const double* x1, const double* x2, const double* ls_env, const double* ls_per,
+                                       const double* period, const double* os, int64_t batch, int64_t n1, int64_t n2,
+                                       int D, int64_t sx1, int64_t sx2, int nu2, const double* G, int64_t ldg,
+                                       int64_t sG, double* g_x1, double* g_x2, double* g_ls_env, double* g_ls_per,
+                                       double* g_period, double* g_os, void* ws, size_t wsb, void* stream) {
+    return matper_bwd<double>(x1, x2, ls_env, ls_per, period, os, batch, n1, n2, D, sx1, sx2, nu2, G, ldg, sG, g_x1,
+                              g_x2, g_ls_env, g_ls_per, g_period, g_os, ws, wsb, stream);
 }
 
 }  // extern "C"

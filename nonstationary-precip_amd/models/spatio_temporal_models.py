@@ -3,29 +3,33 @@ SURVEY 8f.1): a temporal component  ScaleKernel(RBF(t) * Periodic(t), outputscal
 spatial component on columns (1, 2) -- stationary RBF-ARD (exact, or SGPR when inducing points are given),
 or the sparse non-stationary Gibbs kernel with MAP lengthscales at the inducing points.
 
-The temporal factor is ONE launch of the fused RBF x Periodic gfx950 kernel (nsgp.ops.rbf_periodic_kernel);
+The temporal factor is ONE launch of the fused RBF x Periodic gfx950 kernel (nsgp.ops.rbf_periodic_kernel), or of its
+Matern-envelope sibling (nsgp.ops.matern_periodic_kernel) when `temporal_nu` is given;
 Cholesky / triangular work runs on nsgp.ops like the rest of the path."""
 import torch
 
 import nsgp.gp as gpytorch
 from nsgp import ops
 from nsgp.gp.constraints import GreaterThan
-from nsgp.gp.kernels import InducingPointKernel, PeriodicKernel, RBFKernel, ScaleKernel
+from nsgp.gp.kernels import InducingPointKernel, MaternKernel, PeriodicKernel, RBFKernel, ScaleKernel
 from models.gibbs_kernels import GibbsKernel, GibbsSafeScaleKernel, InducingGibbsKernelST
 
 
-def _temporal_kernel():
-    return ScaleKernel(RBFKernel(active_dims=(0)) * PeriodicKernel(active_dims=(0)),
-                       outputscale_constraint=GreaterThan(7), active_dims=0)
+def _temporal_kernel(nu=None):
+    """nu = None: the reference's squared-exponential envelope; 0.5, 1.5 or 2.5: a Matern envelope on the annual cycle
+    (MaternKernel has RBFKernel's parameter names, so state_dict keys do not depend on nu).  Either way one launch."""
+    envelope = RBFKernel(active_dims=(0)) if nu is None else MaternKernel(nu=nu, active_dims=(0))
+    return ScaleKernel(envelope * PeriodicKernel(active_dims=(0)), outputscale_constraint=GreaterThan(7), active_dims=0)
 
 
 class SpatioTemporal_Stationary(gpytorch.models.ExactGP):
-    """k = os_t RBF(t) Periodic(t) + os_s RBF-ARD(lon, lat); SGPR over the sum when `z` is given."""
+    """k = os_t RBF(t) Periodic(t) + os_s RBF-ARD(lon, lat); SGPR over the sum when `z` is given.
+    temporal_nu (keyword-only): None is the RBF envelope, 0.5, 1.5 or 2.5 a Matern envelope in the temporal component."""
 
-    def __init__(self, train_x, train_y, likelihood, z=None):
+    def __init__(self, train_x, train_y, likelihood, z=None, *, temporal_nu=None):
         super().__init__(train_x, train_y, likelihood)
         self.mean_module = gpytorch.means.ZeroMean()
-        self.temporal_covar_module = _temporal_kernel()
+        self.temporal_covar_module = _temporal_kernel(temporal_nu)
         self.spatial_covar_module = ScaleKernel(RBFKernel(active_dims=(1, 2)), active_dims=(1, 2))
         if z is not None:
             self.covar_module = InducingPointKernel(base_kernel=self.temporal_covar_module + self.spatial_covar_module,
@@ -40,16 +44,17 @@ class SpatioTemporal_Stationary(gpytorch.models.ExactGP):
 class SparseSpatioTemporal_Nonstationary(gpytorch.models.ExactGP):
     """MAP inference of the sparse Gibbs-kernel GP over (lon, lat) plus an SGPR temporal component that shares
     the spatial kernel's inducing points (frozen for the temporal part, spatio_temporal_models.py:42-43).
-    nu (keyword-only): None is the Gibbs kernel, 0.5, 1.5 or 2.5 its Matern form (GibbsKernel)."""
+    nu (keyword-only): None is the Gibbs kernel, 0.5, 1.5 or 2.5 its Matern form (GibbsKernel).
+    temporal_nu (keyword-only): the same choice for the temporal component's envelope (None: RBF)."""
 
-    def __init__(self, train_x, train_y, likelihood, prior, z, num_dim=1, *, nu=None):
+    def __init__(self, train_x, train_y, likelihood, prior, z, num_dim=1, *, nu=None, temporal_nu=None):
         super().__init__(train_x, train_y, likelihood)
         self.mean_module = gpytorch.means.ZeroMean()
         self.spatial_covar_module = GibbsSafeScaleKernel(
             InducingGibbsKernelST(GibbsKernel(lengthscale_prior=prior, active_dims=(0, 1), nu=nu), inducing_points=z,
                                   likelihood=likelihood, active_dims=(1, 2)), active_dims=(1, 2))
         self.temporal_covar_module = InducingPointKernel(
-            _temporal_kernel(), inducing_points=self.spatial_covar_module.base_kernel.inducing_points,
+            _temporal_kernel(temporal_nu), inducing_points=self.spatial_covar_module.base_kernel.inducing_points,
             likelihood=likelihood, active_dims=(0))
         self.temporal_covar_module.inducing_points.requires_grad = False
         # gpytorch wraps the very same storage (no copy): the temporal part follows the spatial inducing points

@@ -239,13 +239,15 @@ class ProductKernel(Kernel):
         self.kernels = torch.nn.ModuleList(kernels)
 
     def _rbf_periodic(self):
-        """(rbf, periodic) when this is RBFKernel * PeriodicKernel on the same active dims: one fused launch."""
+        """(envelope, periodic) when this is RBFKernel * PeriodicKernel or MaternKernel * PeriodicKernel, in either order,
+        on the same active dims: one fused launch (the envelope's type picks it, PeriodicKernel.forward)."""
         if len(self.kernels) != 2:
             return None
         a, b = self.kernels
-        if isinstance(a, PeriodicKernel) and isinstance(b, RBFKernel):
+        if isinstance(a, PeriodicKernel) and isinstance(b, (RBFKernel, MaternKernel)):
             a, b = b, a
-        if isinstance(a, RBFKernel) and isinstance(b, PeriodicKernel) and _same_dims(a.active_dims, b.active_dims):
+        if isinstance(a, (RBFKernel, MaternKernel)) and isinstance(b, PeriodicKernel) and \
+                _same_dims(a.active_dims, b.active_dims):
             return a, b
         return None
 
@@ -256,10 +258,10 @@ class ProductKernel(Kernel):
     def forward(self, x1, x2, diag=False, _outputscale=None, **params):
         pair = self._rbf_periodic()
         if pair is not None and not diag:
-            rbf, per = pair
-            if rbf.active_dims is not None:
-                x1, x2 = x1.index_select(-1, rbf.active_dims), x2.index_select(-1, rbf.active_dims)
-            return per.forward(x1, x2, _outputscale=_outputscale, _rbf=rbf)
+            env, per = pair
+            if env.active_dims is not None:
+                x1, x2 = x1.index_select(-1, env.active_dims), x2.index_select(-1, env.active_dims)
+            return per.forward(x1, x2, _outputscale=_outputscale, _rbf=env)
         res = None
         for k in self.kernels:
             nxt = delazify(k(x1, x2, diag=diag, **params))
@@ -275,7 +277,8 @@ class PeriodicKernel(Kernel):
     """exp(-2 sin^2(pi |x1 - x2| / period_length) / lengthscale)  [gpytorch < 1.9 as recalled, SURVEY A.2/A.7:
     Euclidean distance of x / period, division by the lengthscale (not its square)]; used as
     RBFKernel * PeriodicKernel on the time column (models/spatio_temporal_models.py:22,42,
-    experiments/temporal_exp.py:39).  Built by the fused RBF x Periodic gfx950 kernel (nsgp.ops.rbf_periodic_kernel)."""
+    experiments/temporal_exp.py:39).  Built by the fused RBF x Periodic gfx950 kernel (nsgp.ops.rbf_periodic_kernel), or,
+    as MaternKernel * PeriodicKernel, by its Matern-envelope sibling (nsgp.ops.matern_periodic_kernel)."""
     has_lengthscale = True
     is_stationary = True
 
@@ -319,13 +322,17 @@ class PeriodicKernel(Kernel):
             r = d.pow(2).sum(-1).sqrt()
             res = torch.exp(-2.0 * torch.sin(math.pi * r / per.squeeze(-1)).pow(2) / ls.squeeze(-1))
             if _rbf is not None:
-                res = res * torch.exp(-0.5 * (d / _rbf.lengthscale).pow(2).sum(-1))
+                res = res * _rbf._radial((d / _rbf.lengthscale).pow(2).sum(-1))
             if _outputscale is not None:
                 res = res * (_outputscale.unsqueeze(-1) if _outputscale.dim() else _outputscale)
             return res
         xa = x1.reshape(-1, *x1.shape[-2:]) if x1.dim() > 3 else x1
         xb = x2.reshape(-1, *x2.shape[-2:]) if x2.dim() > 3 else x2
-        K = ops.rbf_periodic_kernel(_batched_inputs(xa, B), _batched_inputs(xb, B), ls_rbf, ls_b, per_b, os_)
+        xa, xb = _batched_inputs(xa, B), _batched_inputs(xb, B)
+        if isinstance(_rbf, MaternKernel):                                  # the envelope's type picks the launch
+            K = ops.matern_periodic_kernel(xa, xb, ls_rbf, ls_b, per_b, os_, _rbf.nu)
+        else:
+            K = ops.rbf_periodic_kernel(xa, xb, ls_rbf, ls_b, per_b, os_)
         return K.reshape(*bshape, K.shape[-2], K.shape[-1])
 
 

@@ -326,23 +326,24 @@ def matern_build_bwd(x1, x2, ls, os_, nu, G, need_x1=True, need_x2=True, sym=Fal
 # --------------------------------------------------------------------------------------------
 # K2' RBF-ARD x Periodic (one launch)
 # --------------------------------------------------------------------------------------------
-def _rbfper_args(x1, x2, ls_rbf, ls_per, period, os_):
+def _rbfper_args(x1, x2, ls_rbf, ls_per, period, os_, what='rbf_periodic_build', env='ls_rbf'):
+    """The periodic family's argument rules; `what` and `env` name the op and its envelope lengthscale in the errors."""
     ref = _chk(x1, x2, ls_rbf, ls_per, period, os_)
     ls_per, period = _c(ls_per.reshape(-1)), _c(period.reshape(-1))
     batch = ls_per.shape[0]
     if period.shape[0] != batch:
-        raise BackendError('rbf_periodic_build: ls_per and period must be (batch,)')
+        raise BackendError(f'{what}: ls_per and period must be (batch,)')
     D = x1.shape[-1]
     if ls_rbf is not None:
         ls_rbf = _c(ls_rbf.reshape(batch, -1))
         if ls_rbf.shape[1] != D:
-            raise BackendError('rbf_periodic_build: ls_rbf must be (batch, D)')
+            raise BackendError(f'{what}: {env} must be (batch, D)')
     if os_ is not None:
         os_ = _c(os_.reshape(-1))
         if os_.shape[0] != batch:
-            raise BackendError('rbf_periodic_build: os must be (batch,)')
-    x1, n1, sx1 = _shared_or_batched(x1, batch, D, 'rbf_periodic_build')
-    x2, n2, sx2 = _shared_or_batched(x2, batch, D, 'rbf_periodic_build')
+            raise BackendError(f'{what}: os must be (batch,)')
+    x1, n1, sx1 = _shared_or_batched(x1, batch, D, what)
+    x2, n2, sx2 = _shared_or_batched(x2, batch, D, what)
     return ref, x1, x2, ls_rbf, ls_per, period, os_, batch, n1, n2, D, sx1, sx2
 
 
@@ -373,6 +374,45 @@ def rbf_periodic_build_bwd(x1, x2, ls_rbf, ls_per, period, os_, G, need_x1=True,
               batch, n1, n2, D, sx1, sx2, _p(G), n2, n1 * n2, _p(g_x1), _p(g_x2), _p(g_lr), _p(g_lp), _p(g_pe), _p(g_os),
               _p(ws), ws.numel(), _stream())
     return g_x1, g_x2, g_lr, g_lp, g_pe, g_os
+
+
+# --------------------------------------------------------------------------------------------
+# K2''' Matern-ARD x Periodic (one launch), nu in {1/2, 3/2, 5/2}: the rbf_periodic argument rules, the envelope required
+# --------------------------------------------------------------------------------------------
+def _matper_args(x1, x2, ls_env, ls_per, period, os_, nu):
+    nu2 = _nu2(nu)
+    if ls_env is None:
+        raise BackendError('matern_periodic_build: ls_env is required (the plain PeriodicKernel is rbf_periodic_build)')
+    return (*_rbfper_args(x1, x2, ls_env, ls_per, period, os_, 'matern_periodic_build', 'ls_env'), nu2)
+
+
+def matern_periodic_build(x1, x2, ls_env, ls_per, period, os_, nu, diag_add=0.0):
+    """K[b] = os[b] Matern_nu-ARD(x; ls_env[b]) Periodic(x; ls_per[b], period[b]) (+diag_add I); os_ may be None."""
+    ref, x1, x2, ls_env, ls_per, period, os_, batch, n1, n2, D, sx1, sx2, nu2 = _matper_args(x1, x2, ls_env, ls_per,
+                                                                                            period, os_, nu)
+    K = torch.empty((batch, n1, n2), dtype=ref.dtype, device=ref.device)
+    _lib.call(f'nsgp_matern_periodic_build_fwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls_env), _p(ls_per), _p(period), _p(os_),
+              batch, n1, n2, D, sx1, sx2, nu2, float(diag_add), _p(K), n2, n1 * n2, _stream())
+    return K
+
+
+def matern_periodic_build_bwd(x1, x2, ls_env, ls_per, period, os_, nu, G, need_x1=True, need_x2=True):
+    """As rbf_periodic_build_bwd: g_x1:(batch,n1,D) g_x2:(batch,n2,D) per batch (None when not needed), g_ls_env:(batch,D),
+    g_ls_per, g_period, g_os:(batch,).  For nu = 1/2 the derivative at zero distance is taken as 0."""
+    ref, x1, x2, ls_env, ls_per, period, os_, batch, n1, n2, D, sx1, sx2, nu2 = _matper_args(x1, x2, ls_env, ls_per,
+                                                                                            period, os_, nu)
+    _chk(ref, G)
+    G = _c(G).reshape(batch, n1, n2)
+    new = lambda *shp: torch.empty(shp, dtype=ref.dtype, device=ref.device)
+    g_x1 = new(batch, n1, D) if need_x1 else None
+    g_x2 = new(batch, n2, D) if need_x2 else None
+    g_le, g_lp, g_pe, g_os = new(batch, D), new(batch), new(batch), new(batch)
+    # the periodic family's accumulator layout: one workspace query for both members
+    ws = _ws(_lib.load().nsgp_rbf_periodic_build_bwd_workspace(batch, n1, n2, D, ref.element_size()), ref.device)
+    _lib.call(f'nsgp_matern_periodic_build_bwd_{_sfx(ref)}', _p(x1), _p(x2), _p(ls_env), _p(ls_per), _p(period), _p(os_),
+              batch, n1, n2, D, sx1, sx2, nu2, _p(G), n2, n1 * n2, _p(g_x1), _p(g_x2), _p(g_le), _p(g_lp), _p(g_pe),
+              _p(g_os), _p(ws), ws.numel(), _stream())
+    return g_x1, g_x2, g_le, g_lp, g_pe, g_os
 
 
 # --------------------------------------------------------------------------------------------
@@ -1476,13 +1516,18 @@ class MaternKernelFn(torch.autograd.Function):
 
 class RbfPeriodicKernelFn(torch.autograd.Function):
     """K[b] = os[b] RBF-ARD(x; ls_rbf[b]) Periodic(x; ls_per[b], period[b]) + diag_add I; ls_rbf / os may be None
-    (gpytorch ScaleKernel(RBFKernel * PeriodicKernel), models/spatio_temporal_models.py:22,42)."""
+    (gpytorch ScaleKernel(RBFKernel * PeriodicKernel), models/spatio_temporal_models.py:22,42).
+    nu = None: that kernel; 0.5, 1.5, 2.5: the Matern envelope in place of the RBF one (ls_rbf is then its lengthscale and
+    required) -- one node for the periodic family, as GibbsKernelFn and Ps2dKernelFn are for theirs."""
 
     @staticmethod
-    def forward(ctx, x1, x2, ls_rbf, ls_per, period, os_, diag_add):
+    def forward(ctx, x1, x2, ls_rbf, ls_per, period, os_, diag_add, nu=None):
         ctx.save_for_backward(x1, x2, ls_per, period, *([ls_rbf] if ls_rbf is not None else []),
                               *([os_] if os_ is not None else []))
         ctx.has = (ls_rbf is not None, os_ is not None)
+        ctx.nu = nu
+        if nu is not None:
+            return matern_periodic_build(x1, x2, ls_rbf, ls_per, period, os_, nu, diag_add)
         return rbf_periodic_build(x1, x2, ls_rbf, ls_per, period, os_, diag_add)
 
     @staticmethod
@@ -1492,10 +1537,14 @@ class RbfPeriodicKernelFn(torch.autograd.Function):
         ls_rbf = rest.pop(0) if ctx.has[0] else None
         os_ = rest.pop(0) if ctx.has[1] else None
         n1g, n2g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        g_x1, g_x2, g_lr, g_lp, g_pe, g_os = rbf_periodic_build_bwd(x1, x2, ls_rbf, ls_per, period, os_, G, n1g, n2g)
+        if ctx.nu is not None:
+            g_x1, g_x2, g_lr, g_lp, g_pe, g_os = matern_periodic_build_bwd(x1, x2, ls_rbf, ls_per, period, os_, ctx.nu, G,
+                                                                           n1g, n2g)
+        else:
+            g_x1, g_x2, g_lr, g_lp, g_pe, g_os = rbf_periodic_build_bwd(x1, x2, ls_rbf, ls_per, period, os_, G, n1g, n2g)
         return (_sum_shared(g_x1, x1, n1g), _sum_shared(g_x2, x2, n2g),
                 g_lr.reshape(ls_rbf.shape) if ls_rbf is not None else None, g_lp.reshape(ls_per.shape),
-                g_pe.reshape(period.shape), g_os.reshape(os_.shape) if os_ is not None else None, None)
+                g_pe.reshape(period.shape), g_os.reshape(os_.shape) if os_ is not None else None, None, None)
 
 
 class Ps2dKernelFn(torch.autograd.Function):
@@ -1617,6 +1666,12 @@ def matern_kernel(x1, x2, ls, os_, nu, diag_add=0.0):
 def rbf_periodic_kernel(x1, x2, ls_rbf, ls_per, period, os_=None, diag_add=0.0):
     """Batched (batch, n1, n2): os * RBF-ARD(ls_rbf) * Periodic(ls_per, period); ls_rbf / os_ None = factor absent."""
     return RbfPeriodicKernelFn.apply(x1, x2, ls_rbf, ls_per, period, os_, diag_add)
+
+
+def matern_periodic_kernel(x1, x2, ls_env, ls_per, period, os_=None, nu=2.5, diag_add=0.0):
+    """Batched (batch, n1, n2): os * Matern_nu-ARD(ls_env) * Periodic(ls_per, period), nu in {0.5, 1.5, 2.5}; os_ None = 1."""
+    _nu2(nu)
+    return RbfPeriodicKernelFn.apply(x1, x2, ls_env, ls_per, period, os_, diag_add, nu)
 
 
 def ps2d_kernel(x1, x2, s1, s2, jitter=1e-5, nu=None):
