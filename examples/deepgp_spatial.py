@@ -8,7 +8,9 @@ DeepApproximateMLL(VariationalELBO(likelihood, model, N_train)), Adam(lr=0.01) o
 minibatches of 315, S likelihood samples, then model.predict() and rmse*stdy / nlpd
 (utils/metrics.py:36-45) -- written against this repo's drop-in packages.  Prints one line per split and
 the mean +- standard error over splits; `--out` writes the `,pred,std,lat,lon`-style prediction CSV of
-the last split (the layout of the reference's results/*.csv).
+the last split (the layout of the reference's results/*.csv).  `--init-inducing` starts every layer's inducing points
+from the k-means centres of the training inputs (DeepGP.initialize_inducing_points, on the GPU) instead of the reference's
+Z ~ randn.
 
     python examples/deepgp_spatial.py --splits 2 --epochs 100 --layers 1 --samples 3
 """
@@ -42,6 +44,8 @@ def run_split(dataset, random_state, args, device):
                      likelihood=StudentTLikelihood() if likelihood == 'student_t' else None).to(device)
     mll = DeepApproximateMLL(VariationalELBO(model.likelihood, model, train_x.shape[-2]))
     train_x, train_y, test_x, test_y = (t.to(device) for t in (train_x, train_y, test_x, test_y))
+    if getattr(args, 'init_inducing', False):
+        model.initialize_inducing_points(train_x, seed=random_state)
     loader = DataLoader(TensorDataset(train_x, train_y), batch_size=args.batch, shuffle=True)
     model.train()
     optimizer = torch.optim.Adam([{'params': model.parameters()}], lr=args.lr)
@@ -98,6 +102,8 @@ def main():
     ap.add_argument('--likelihood', choices=('gaussian', 'student_t'), default='gaussian',
                     help="observation model: Gaussian noise (the reference) or the outlier-robust Student-t, whose ELBO "
                          "term is a 20-node Gauss-Hermite sum in torch ops")
+    ap.add_argument('--init-inducing', action='store_true',
+                    help='inducing points from k-means of the training inputs (default: Z ~ randn, as the reference)')
     ap.add_argument('--lr', type=float, default=0.01)
     ap.add_argument('--out', default=None)
     ap.add_argument('--verbose', action='store_true')

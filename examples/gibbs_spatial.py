@@ -12,7 +12,8 @@ rmse*stdy / nlpd (utils/metrics.py:36-45) and model.predict(x) for the full-fiel
 train-sized `ell1` through gpytorch's joint [train; test] covariance and is shape-inconsistent for this
 kernel; `predict()` (models/nonstationary_models.py:45-62) is the model's own predictive and is what is used here.)
 `--inference sparse --M 250` runs DiagonalSparseGP with k-means inducing points instead
-(scikit-learn's KMeans; the reference uses pymc3's helper, spatial_exp.py:153).
+(scikit-learn's KMeans by default; `--kmeans native` picks them on the GPU with nsgp.kmeans_inducing_points, the call
+shape of the pymc3 helper the reference uses at spatial_exp.py:153).
 `--nu 0.5 | 1.5 | 2.5` (no reference counterpart) swaps the squared-exponential Gibbs kernel for its Matern form,
 GibbsKernel(nu=...): the same lengthscale field, a rougher prior on the precipitation field.
 
@@ -43,6 +44,8 @@ def main():
     ap.add_argument('--iters', type=int, default=5000)
     ap.add_argument('--inference', choices=('exact', 'sparse'), default='exact')
     ap.add_argument('--M', type=int, default=250)
+    ap.add_argument('--kmeans', choices=('sklearn', 'native'), default='sklearn',
+                    help='inducing points of --inference sparse: scikit-learn on the host, or the HIP k-means on the GPU')
     ap.add_argument('--nu', type=float, choices=(0.5, 1.5, 2.5), default=None,
                     help='non-stationary Matern kernel with this smoothness (default: the Gibbs kernel)')
     ap.add_argument('--prior_scale', type=float, default=1.0)
@@ -87,9 +90,13 @@ def main():
         if args.inference == 'exact':
             model = DiagonalExactGP(x_train, y_train, likelihood, prior, num_dim=2, nu=args.nu).to(device).double()
         else:
-            from sklearn.cluster import KMeans
-            z = torch.tensor(KMeans(args.M, n_init=1, random_state=BASE_SEED + i).fit(x_train.cpu().numpy())
-                             .cluster_centers_).double()
+            if args.kmeans == 'native':
+                from nsgp import kmeans_inducing_points
+                z = kmeans_inducing_points(args.M, x_train, seed=BASE_SEED + i)
+            else:
+                from sklearn.cluster import KMeans
+                z = torch.tensor(KMeans(args.M, n_init=1, random_state=BASE_SEED + i).fit(x_train.cpu().numpy())
+                                 .cluster_centers_).double()
             model = DiagonalSparseGP(x_train, y_train, likelihood, prior, z, num_dim=2, nu=args.nu).to(device).double()
         if args.noise > 0:
             model.likelihood.noise = args.noise

@@ -6,7 +6,9 @@ SGPR) or SparseSpatioTemporal_Nonstationary (`--model Non-Stationary`), Adam(lr=
 -ExactMarginalLogLikelihood for 500 iterations, then likelihood(model(x_test)) [stationary] or
 likelihood(model.predict(x_test)) [non-stationary], rmse * stdy and the Gaussian NLPD of utils/metrics.py.
 `--temporal-nu 0.5|1.5|2.5` gives the temporal component a Matern envelope (MaternKernel(nu) * PeriodicKernel, one fused
-launch) in either model; without it the run is the reference's.
+launch) in either model; without it the run is the reference's.  `--kmeans native` picks the inducing points on the GPU
+(nsgp.kmeans_inducing_points, the call shape of the helper commented out at spatio_temporal_exp.py:105) instead of
+scikit-learn's KMeans on the host.
 
     python examples/spatio_temporal.py --iters 300
     python examples/spatio_temporal.py --iters 300 --temporal-nu 1.5
@@ -46,6 +48,8 @@ def main():
     ap.add_argument('--model', choices=('Stationary', 'Non-Stationary'), default='Stationary')
     ap.add_argument('--iters', type=int, default=500)
     ap.add_argument('--M', type=int, default=0, help='inducing points (0: exact GP; Non-Stationary needs M > 0)')
+    ap.add_argument('--kmeans', choices=('sklearn', 'native'), default='sklearn',
+                    help='where the inducing points come from: scikit-learn on the host, or the HIP k-means on the GPU')
     ap.add_argument('--lr', type=float, default=0.015)
     ap.add_argument('--temporal-nu', type=float, choices=(0.5, 1.5, 2.5), default=None,
                     help='Matern envelope of the temporal component (default: the RBF envelope)')
@@ -54,9 +58,12 @@ def main():
         raise SystemExit('examples/spatio_temporal.py needs the MI355X: nsgp has no CPU path')
     x_train, y_train, x_test, y_test, stdy = load_train_test(args.csv)
     z = None
-    if args.M > 0 or args.model == 'Non-Stationary':
+    m = args.M if args.M > 0 else 50 if args.model == 'Non-Stationary' else 0
+    if m and args.kmeans == 'native':
+        from nsgp import kmeans_inducing_points
+        z = kmeans_inducing_points(m, x_train.cuda(), seed=173).cpu()
+    elif m:
         from sklearn.cluster import KMeans
-        m = args.M if args.M > 0 else 50
         z = torch.tensor(KMeans(m, n_init=1, random_state=173).fit(x_train.numpy()).cluster_centers_, dtype=x_train.dtype)
     likelihood = gpytorch.likelihoods.GaussianLikelihood()
     if args.model == 'Stationary':

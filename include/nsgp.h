@@ -26,6 +26,8 @@ extern "C" {
 #endif
 
 #define NSGP_MAX_DIM 8          /* input dimension D supported by the pairwise kernels */
+#define NSGP_KMEANS_MAX_N 2147483647   /* points of a k-means call: the per-cluster counts are int32 */
+#define NSGP_KMEANS_MAX_M 16777216     /* centres of a k-means call (2^24): the update's grid has ceil(M / 1024) rows */
 
 /* library / device identification (host) */
 int nsgp_abi_version(void);                 /* bumps when a signature changes or an entry point goes; now 2 */
@@ -771,6 +773,43 @@ int nsgp_philox_normal_f64(uint64_t seed, uint64_t stream_id, const int64_t* ste
 int nsgp_adam_step_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t n,
                        float lr, float beta1, float beta2, float eps, int64_t step, const int64_t* step_dev,
                        float grad_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * KM  Lloyd's k-means for the inducing points (csrc/kmeans.hip)
+ *     replaces pm.gp.util.kmeans_inducing_points(num_inducing, x_train) at experiments/spatial_exp.py:153 (pymc3 over
+ *     scipy.cluster.vq.kmeans, on the host).  x:(n,D) row-major with leading dimension ldx >= D; c:(M,D), c_old, c_new
+ *     contiguous; D <= NSGP_MAX_DIM, 1 <= M <= NSGP_KMEANS_MAX_M, n <= NSGP_KMEANS_MAX_N.  n = 0 is valid (assign launches
+ *     nothing; update finds every cluster empty).
+ *
+ *  assign: labels[i] (int32) = the nearest centre of point i and d2[i] its squared distance, the chain s = fma(x_d - c_d,
+ *     x_d - c_d, s) over d in order from s = 0 (never |x|^2 + |c|^2 - 2 x.c).  The running best starts at (+inf, 0) and is
+ *     replaced on a strict < only: the lowest index wins a tie, a point with a NaN coordinate keeps (label 0, d2 = +inf)
+ *     and disturbs no other point, and a NaN centre is never chosen.
+ *
+ *  update: c_new[k] = mean of the points labelled k; counts[k] (int32) their number; an empty cluster keeps c_old[k] bit
+ *     for bit with count 0; a label outside [0, M) belongs to no cluster.  stats (2 x float64, device):
+ *     stats[0] = sum_i d2[i] (inertia), stats[1] = sum_k |c_new[k] - c_old[k]|^2 (differences taken in float64).
+ *     Sums run in float64 for both types, a cluster's coordinate sums compensated (two-sum: a high and a low part, so the
+ *     numerator of a mean is the exact sum rounded once); a mean is one float64 division rounded once to the type.
+ *     Deterministic: no floating-point atomics, and the order of every sum depends on (n, D, M) alone.  Three launches:
+ *     per-chunk partial sums [chunk][2 D + 1][M] (high parts, low parts, count; a workgroup stages 512 points at a time
+ *     in LDS, thread t owns clusters t, t + 256, ... and walks the points in order), the per-cluster sum over chunks in chunk order with the division, and the two scalars in one
+ *     workgroup.  A chunk is 512 * clamp(ceil(n / 2^19), 1, 8) points.  A cluster's shift is sum_d of the rounded squares,
+ *     added in d order (no FMA); each scalar is summed as: thread t of 256 adds items t, t + 256, ... in order, a xor
+ *     butterfly over each wave's 64 lanes (offsets 32 .. 1), then the four waves in order.
+ *     ws: nsgp_kmeans_update_workspace(n, D, M) = 8 (chunks (2 D + 1) M + chunks + M) bytes (0 for an invalid argument).
+ * ------------------------------------------------------------------------------------------ */
+int nsgp_kmeans_assign_f32(const float* x, int64_t ldx, int64_t n, int D, const float* c, int M, int32_t* labels,
+                           float* d2, void* stream);
+int nsgp_kmeans_assign_f64(const double* x, int64_t ldx, int64_t n, int D, const double* c, int M, int32_t* labels,
+                           double* d2, void* stream);
+size_t nsgp_kmeans_update_workspace(int64_t n, int D, int M);
+int nsgp_kmeans_update_f32(const float* x, int64_t ldx, int64_t n, int D, const int32_t* labels, const float* d2,
+                           const float* c_old, int M, float* c_new, int32_t* counts, double* stats, void* ws,
+                           void* stream);
+int nsgp_kmeans_update_f64(const double* x, int64_t ldx, int64_t n, int D, const int32_t* labels, const double* d2,
+                           const double* c_old, int M, double* c_new, int32_t* counts, double* stats, void* ws,
+                           void* stream);
 
 #ifdef __cplusplus
 }

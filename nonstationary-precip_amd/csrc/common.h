@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <mutex>
+#include <type_traits>
 #include <unordered_set>
 #include "../../include/nsgp.h"
 
@@ -27,6 +28,14 @@ static inline void nsgp_opt_in_lds(const void* kern, size_t lds) {
     std::lock_guard<std::mutex> lk(mu);
     if (done.insert(key).second)
         (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+// The one dispatch on the runtime dimension: f(std::integral_constant<int, D>{}) when D is one of the specialised
+// dimensions Ds, else f(std::integral_constant<int, 0>{}) (the generic functor or kernel: NSGP_MAX_DIM slots, runtime trip count).
+template <int... Ds, typename F> int dispatch_dim(int D, F&& f) {
+    int r = 0;
+    const bool hit = ((D == Ds && ((r = f(std::integral_constant<int, Ds>{})), true)) || ...);
+    return hit ? r : f(std::integral_constant<int, 0>{});
 }
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

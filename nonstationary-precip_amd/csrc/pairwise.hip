@@ -813,14 +813,7 @@ template <typename T> OutDesc<T> empty_desc(int nval) {
 // ------------------------------------------------------------------------------------------
 // typed entry points
 // ------------------------------------------------------------------------------------------
-// The one dispatch on the runtime dimension: f(std::integral_constant<int, D>{}) when D is one of the specialised
-// dimensions Ds, else f(std::integral_constant<int, 0>{}) (the generic functor: NSGP_MAX_DIM slots, runtime trip count).
-template <int... Ds, typename F> int dispatch_dim(int D, F&& f) {
-    int r = 0;
-    const bool hit = ((D == Ds && ((r = f(std::integral_constant<int, Ds>{})), true)) || ...);
-    return hit ? r : f(std::integral_constant<int, 0>{});
-}
-
+// dispatch_dim (common.h) is the one dispatch on the runtime dimension.
 template <typename T>
 int gibbs_fwd(const T* x1, const T* x2, const T* l1, const T* l2, int64_t n1, int64_t n2, int D, const T* os,
               const T* diag_add, T* K, int64_t ldk, void* stream) {

@@ -85,6 +85,27 @@ class DeepGP(_DeepGPBase):
             rep = layer(rep)
         return self.last_layer(rep)
 
+    def initialize_inducing_points(self, x, *, seed=0, **kmeans_kw):
+        """Replace the Z ~ randn start (a reference quirk, kept as the default) by k-means: the first layer's Z becomes the
+        centres `nsgp.cluster.kmeans(x, num_inducing, seed=seed, **kmeans_kw)` of the inputs x:(n, D), shared by its output
+        dimensions; every later distinct layer, the last included, gets those centres pushed through the mean modules of the
+        layers before it (a tied hidden layer is set once and applied num_layers times).  Nothing else changes.  Returns
+        the KMeansResult."""
+        from nsgp.cluster import kmeans
+        first = self.layers[0].variational_strategy.inducing_points
+        res = kmeans(x, first.shape[-2], seed=seed, **kmeans_kw)
+        rep, done = res.centers.to(first.dtype), set()
+        with torch.no_grad():
+            for layer in list(self.layers) + [self.last_layer]:
+                if id(layer) not in done:
+                    done.add(id(layer))
+                    Z = layer.variational_strategy.inducing_points
+                    Z.copy_(rep.expand_as(Z))
+                if layer is not self.last_layer:
+                    m = layer.mean_module(rep)                          # (M,), or (output_dims, M) for a batched mean
+                    rep = m.unsqueeze(-1).expand(-1, layer.output_dims) if m.dim() == 1 else m.transpose(-1, -2)
+        return res
+
     def predict(self, test_loader):
         """Returns (predictive of the LAST batch, means (S,N), variances (S,N), per-point log marginals (S,N)):
         the tuple of the reference's DeepGP.predict (:100-111).  Each batch is propagated twice, once for the

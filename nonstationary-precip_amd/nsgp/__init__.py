@@ -6,5 +6,8 @@ anywhere, but every op needs the built library and CUDA tensors (`BackendError` 
 """
 from ._lib import BackendError, LIB_PATH, declared_symbols, load as load_library  # noqa: F401
 from . import ops  # noqa: F401
+from . import cluster  # noqa: F401
+from .cluster import KMeansResult, kmeans, kmeans_inducing_points  # noqa: F401
 
-__all__ = ['BackendError', 'LIB_PATH', 'declared_symbols', 'load_library', 'ops']
+__all__ = ['BackendError', 'LIB_PATH', 'declared_symbols', 'load_library', 'ops', 'cluster', 'KMeansResult', 'kmeans',
+           'kmeans_inducing_points']

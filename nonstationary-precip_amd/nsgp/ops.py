@@ -480,6 +480,57 @@ def pairwise_bwd_plan(batch, n1, n2):
 
 
 # --------------------------------------------------------------------------------------------
+# KM Lloyd's k-means (include/nsgp.h, KM; nsgp.cluster drives the loop).  Raw ops, no autograd.
+# --------------------------------------------------------------------------------------------
+def _kmeans_x(x, c, what):
+    """(x as the kernel reads it, ldx, n, D): any 2-D x with unit column stride and row stride >= D goes in without a copy."""
+    ref = _chk(x, c)
+    if x.dim() != 2 or c.dim() != 2 or c.shape[1] != x.shape[1] or c.shape[0] < 1:
+        raise BackendError(f'{what}: x:(n,D), centres:(M>=1,D) expected, got {tuple(x.shape)} and {tuple(c.shape)}')
+    n, D = x.shape
+    if (D > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) < D):
+        x = x.contiguous()
+    return ref, x, max(x.stride(0), D), n, D
+
+
+def _kmeans_vec(t, n, dtype, ref, name):
+    if t.shape != (n,) or t.dtype != dtype or t.device != ref.device or not t.is_contiguous():
+        raise BackendError(f'{name}: contiguous ({n},) {dtype} tensor on {ref.device} expected')
+    return t
+
+
+def kmeans_assign(x, c, labels=None, d2=None):
+    """(labels int32 (n,), d2 (n,)): the nearest of the M centres c:(M,D) of every point of x:(n,D) and the squared distance
+    to it (FMA chain on differences; strict <, so the lowest index wins a tie; a NaN point keeps label 0 and d2 = +inf).
+    `labels` / `d2`: buffers to write into."""
+    ref, x, ldx, n, D = _kmeans_x(x, c, 'kmeans_assign')
+    c = _c(c)
+    labels = torch.empty(n, dtype=torch.int32, device=ref.device) if labels is None \
+        else _kmeans_vec(labels, n, torch.int32, ref, 'labels')
+    d2 = torch.empty(n, dtype=ref.dtype, device=ref.device) if d2 is None else _kmeans_vec(d2, n, ref.dtype, ref, 'd2')
+    _lib.call(f'nsgp_kmeans_assign_{_sfx(ref)}', _p(x), ldx, n, D, _p(c), c.shape[0], _p(labels), _p(d2), _stream())
+    return labels, d2
+
+
+def kmeans_update(x, labels, d2, c_old):
+    """(c_new (M,D), counts int32 (M,), stats float64 (2,) = [sum d2, sum_k |c_new_k - c_old_k|^2]): the mean of every
+    cluster's points, float64 sums in an order fixed by (n, D, M), one division; an empty cluster keeps c_old bit for bit."""
+    ref, x, ldx, n, D = _kmeans_x(x, c_old, 'kmeans_update')
+    _chk(ref, d2)
+    c_old = _c(c_old)
+    M = c_old.shape[0]
+    _kmeans_vec(labels, n, torch.int32, ref, 'labels')
+    _kmeans_vec(d2, n, ref.dtype, ref, 'd2')
+    c_new = torch.empty_like(c_old)
+    counts = torch.empty(M, dtype=torch.int32, device=ref.device)
+    stats = torch.empty(2, dtype=torch.float64, device=ref.device)
+    ws = _ws(_lib.load().nsgp_kmeans_update_workspace(n, D, M), ref.device)
+    _lib.call(f'nsgp_kmeans_update_{_sfx(ref)}', _p(x), ldx, n, D, _p(labels), _p(d2), _p(c_old), M, _p(c_new), _p(counts),
+              _p(stats), _p(ws), _stream())
+    return c_new, counts, stats
+
+
+# --------------------------------------------------------------------------------------------
 # MFMA GEMM
 # --------------------------------------------------------------------------------------------
 def _mat_view(t, trans):
